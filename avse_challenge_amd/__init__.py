@@ -21,7 +21,30 @@ B=32 step on a fresh box, vs ~8 s with the records.
 import os
 
 MIOPEN_DB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "miopen_db")
-os.environ.setdefault("MIOPEN_USER_DB_PATH", MIOPEN_DB)     # read by MIOpen at handle creation
+
+
+def _miopen_user_db():
+    """MIOpen appends the shapes it meets to its user find-db (and writes a .time file beside it): it gets a working
+    copy of the committed records under build/ (beside the kernels' object files), so a run leaves the committed file
+    as it is.  A record file is copied when the copy is missing or older; where build/ cannot be written, MIOpen
+    reads the records in place."""
+    import shutil
+    dst = os.path.join(os.path.dirname(os.path.dirname(MIOPEN_DB)), "build", "miopen_db")
+    try:
+        os.makedirs(dst, exist_ok=True)
+        for name in os.listdir(MIOPEN_DB):
+            src, out = os.path.join(MIOPEN_DB, name), os.path.join(dst, name)
+            if not os.path.exists(out) or os.path.getmtime(out) < os.path.getmtime(src):
+                tmp = f"{out}.{os.getpid()}.tmp"
+                shutil.copyfile(src, tmp)
+                os.replace(tmp, out)                   # atomic: several ranks may start at once
+    except OSError:
+        return MIOPEN_DB
+    return dst
+
+
+if "MIOPEN_USER_DB_PATH" not in os.environ:
+    os.environ["MIOPEN_USER_DB_PATH"] = _miopen_user_db()    # read by MIOpen at handle creation
 
 # HIP graphs: the runtime's graph packet capture (ROCm 7.x CLR; AQL packets and kernel arguments prepared at
 # instantiate time) replays some kernel nodes of the long single-stream avse1 train-step graph with the wrong

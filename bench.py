@@ -1,6 +1,11 @@
 """Throughput bench: utterances/s of the avse1 AV training step on MI355X (BASELINE configs[1]).
 
 python bench.py [--gpus N --steps K --warmup W --workload avse1|mamba|avse4|avmamba|dpmamba|avse2]
+                [--full] [--dump-outputs DIR]
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what the headline figure does not
+need: the rooflines, the CPU baseline, the parity check vs the oracle and the secondary configs.  --dump-outputs DIR
+puts the seeded start state back after the timed steps, calls the timed step once more and writes its loss and
+gradients as DIR/<name>.npy (they repeat from run to run up to the rounding of that one step).
 One rank per GPU over RCCL: under torch.distributed.run (RANK / WORLD_SIZE in the env), or, with
 --gpus N > 1 and no WORLD_SIZE, bench.py starts N ranks itself (a torch.distributed.run child
 process launched before anything touches the GPU) and exits with its status. Every rank trains on
@@ -17,7 +22,7 @@ A step = one pass of the hot path over one batch, inputs already resident in HBM
                -> SI-SNR loss -> bwd -> Adam (C4: 16 per GPU).
   avmamba (C5): Mamba-TasNet-L + avse4 lip encoder, bf16 autocast, B x 3 s @ 16 kHz (L = 5999) + 75 lip
                frames 112x112 -> SI-SNR loss -> bwd -> Adam (C5: 32 per GPU).
-Rank 0 prints ONE JSON line (plus "roofline" for the dominant kernel, timed live with HIP
+Rank 0 prints ONE JSON line (with --full plus "roofline" for the dominant kernel, timed live with HIP
 events on torch's current stream, and "cpu_baseline": the oracle restatement on host cores).
 """
 import argparse
@@ -45,6 +50,8 @@ METRIC = "utterances/sec (3s@16kHz + 75 lip frames)"
 # HBM bytes per launch of each roofline kernel, from rocprofv3 PMC passes (tools/pmc_traffic.sh:
 # FETCH_SIZE and WRITE_SIZE in separate passes, corrected as MI355X_MICROARCH.md prescribes)
 TRAFFIC_FILE = os.path.join(REPO, "profiles", "r06_traffic.json")   # tools/runs/r06ad.sh (final round-6 tree)
+SEED = 20240                   # initial weights and dropout (rank r: SEED + r); the batches carry seeds of their own
+DUMP_MAX_ELEMS = 4 << 20       # --dump-outputs: at most this many float32 per array (16 MiB)
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md chip table (spec)
 FP32_PEAK_TFS = 157.3          # FP32 matrix (= vector) peak, spec
 
@@ -59,6 +66,17 @@ def parse():
     p.add_argument("--device", default="cuda", choices=["cuda", "cpu"],
                    help="cpu: gloo test hook of the distributed plumbing (--workload plumbing only)")
     p.add_argument("--bucket-mb", type=float, default=25.0, help="gradient all-reduce bucket size (world > 1)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also measure and check everything beside the headline figure: the "
+                        "in-step and isolated rooflines, the north-star kernel list, the CPU baseline, the parity "
+                        "check vs the oracle and the secondary configs (each has its own --no-... switch); without "
+                        "it the run sets up, warms up, times the steps and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps put the model and optimizer back to the seeded start state, call the "
+                        "timed step once more and write what it computed to DIR/<name>.npy (float32): the loss and "
+                        f"the parameters' gradients (a fixed, seeded sample above {DUMP_MAX_ELEMS} elements); the "
+                        "inputs, weights and dropout are seeded, so the arrays repeat from run to run up to the "
+                        "rounding of one step and two builds can be compared output for output")
     p.add_argument("--no-roofline-hip", action="store_true", help="skip the north-star kernel roofline list")
     p.add_argument("--batch", type=int, default=None, help="per-GPU batch (default: the BASELINE config's)")
     p.add_argument("--size", default="L", choices=["XS", "S", "M", "L"], help="Mamba-TasNet / DPMamba size")
@@ -75,7 +93,50 @@ def parse():
     p.add_argument("--direction-streams", default="auto", choices=["auto", "on", "off"],
                    help="Mamba workloads: BiMamba v2's backward direction on a second HIP stream (auto: off, "
                         "the measured default)")
-    return p.parse_args()
+    args = p.parse_args()
+    if not args.full:           # a plain run: set up, warm up, time the steps, print the line
+        args.no_roofline = args.no_roofline_hip = args.no_cpu_baseline = args.no_parity = True
+        args.secondary = ""
+    return args
+
+
+def snapshot_state(work):
+    """--dump-outputs: a copy of the seeded start state (parameters and buffers), taken before the first step."""
+    return {k: v.detach().clone() for k, v in work.model.state_dict().items()}
+
+
+def restore_state(work, step, snap, seed):
+    """Put the model and the optimizer back to the start state IN PLACE (the captured graphs keep the tensors'
+    addresses): parameters and buffers from ``snap``, Adam's moments and step counts to zero, the dropout generators
+    reseeded.  The next call of the timed step then computes from the same inputs and the same state in every run:
+    a chain of steps does not (atomic accumulation in the weight gradients rounds differently from run to run, and
+    Adam turns the rounding noise of a near-zero gradient into a step of +-lr, which the next steps amplify)."""
+    with torch.no_grad():
+        for k, v in work.model.state_dict().items():
+            v.copy_(snap[k])
+        for st in step.opt.state.values():
+            for v in st.values():
+                if torch.is_tensor(v):
+                    v.zero_()
+    torch.manual_seed(seed)
+
+
+def dump_outputs(path, work, loss):
+    """--dump-outputs: what one call of the timed step from the seeded start state (restore_state) computed, as float32
+    DIR/<name>.npy: the loss it returned and the gradients it left on the parameters, flattened in registration order
+    (above DUMP_MAX_ELEMS elements: a seeded sample of positions, in increasing order).  The updated parameters are
+    not written: on the first step Adam moves a parameter by lr * g / (|g| + 1e-8), so where |g| is near 1e-8 the
+    rounding of g (1e-10, atomic accumulation) shows as 1e-5 in the parameter -- no figure to compare builds by."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    params = [p for p in work.model.parameters() if p.requires_grad]
+    grads = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().float().reshape(-1)
+                       for p in params]).cpu()
+    if grads.numel() > DUMP_MAX_ELEMS:
+        idx = torch.randperm(grads.numel(), generator=torch.Generator().manual_seed(2024))[:DUMP_MAX_ELEMS].sort().values
+        grads = grads[idx]
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
+    np.save(os.path.join(path, "grads.npy"), grads.numpy())
 
 
 def run_secondary(args):
@@ -86,7 +147,7 @@ def run_secondary(args):
         # 2 warm-up steps: the in-step roofline taps the last one, past the first step's one-time work (MIOpen's
         # first-call solver selection ran its naive fallback kernels there: 0.5 s per C4 / C5 step, r06i profiles)
         cmd = [sys.executable, os.path.abspath(__file__), "--workload", wl, "--steps", str(args.secondary_steps),
-               "--warmup", "2", "--secondary", "", "--no-cpu-baseline", "--no-roofline-hip"]
+               "--warmup", "2", "--full", "--secondary", "", "--no-cpu-baseline", "--no-roofline-hip"]
         t = time.perf_counter()
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
@@ -1172,6 +1233,7 @@ def main():
         torch.backends.cudnn.benchmark = bool(int(os.environ.get("AVSE_MIOPEN_FIND", "0")))
     global DIRECTION_STREAMS_ARG
     DIRECTION_STREAMS_ARG = args.direction_streams
+    torch.manual_seed(SEED + rank)      # same initial weights and dropout masks from run to run
     if args.workload == "avse1":
         B = args.batch or 32
         work = Avse1Step(B, dev, rank, world, args.lip_hw)
@@ -1198,6 +1260,7 @@ def main():
 
     use_graph = work.graph_ok and not args.no_graph and dev.type == "cuda"
     step = Trainer(work, world, dev, use_graph=use_graph, bucket_mb=args.bucket_mb)
+    snap = snapshot_state(work) if args.dump_outputs else None
     # in-step roofline of C3 / C4 / C5: every launch of the workload's dominant hand-written kernels inside the last
     # eager warm-up step (the same kernels, streams and concurrency the captured step replays), HIP events on each
     # launch's stream (kernels.LAUNCH_TAPS).  AVSE_PROFILE_MARK=roof brackets that step with marker kernels instead of
@@ -1267,6 +1330,16 @@ def main():
     if not torch.isfinite(loss.detach()).all():
         raise RuntimeError("non-finite loss in the timed region")
     step.check_kernel_errors()          # a grouped-LSTM launch that was not co-resident raises here (ddp.py)
+    if args.dump_outputs:
+        # one more call of the timed step (the same captured graphs), from the seeded start state: its results are
+        # the same in every run up to the rounding of one step, whatever --steps and --warmup are (restore_state)
+        restore_state(work, step, snap, SEED + rank)
+        loss = step()
+        sync(dev)
+        step.check_kernel_errors()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, work, loss)
+        del snap
 
     cuda = dev.type == "cuda"
     roof = None if args.no_roofline or rank != 0 or not cuda else work.roofline(dev)

@@ -237,6 +237,34 @@ def test_ddp_batchnorm_model_world2_matches_ddp_semantics(bucket_mb):
         assert r0["hook_launches"] == (STEPS - 1) * r0["n_buckets"], (r0["hook_launches"], r0["n_buckets"])
 
 
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """--dump-outputs DIR writes the loss and the gradients of one call of the timed step from the seeded start
+    state as float32 DIR/<name>.npy: two runs with the same arguments write the same arrays, and so does a run with
+    another --steps (the state is put back before that call); the line carries steps and ms_per_step."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    dumps = []
+    for tag, steps in (("a", 2), ("b", 2), ("c", 3)):
+        out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--device", "cpu",
+                              "--workload", "plumbing", "--steps", str(steps), "--warmup", "1",
+                              "--dump-outputs", str(tmp_path / tag)],
+                             capture_output=True, text=True, timeout=300, env=env, cwd=str(tmp_path))
+        assert out.returncode == 0, out.stderr[-3000:]
+        rec = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+        assert rec["steps"] == steps and rec["ms_per_step"] > 0
+        assert abs(rec["value"] * rec["ms_per_step"] - 1e3 * rec["config"]["global_batch"]) <= 1e-2 * 1e3
+        assert sorted(os.listdir(tmp_path / tag)) == ["grads.npy", "loss.npy"]
+        dumps.append({n: np.load(tmp_path / tag / f"{n}.npy") for n in ("loss", "grads")})
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in dumps[-1].values())
+        assert sum(a.nbytes for a in dumps[-1].values()) <= 64 << 20
+    a, b, c = dumps
+    assert a["loss"].shape == (1,) and a["grads"].ndim == 1 and a["grads"].size > 1000
+    # same inputs, same arithmetic: fp32 rounding of a different reduction order at the most
+    assert all(np.allclose(a[n], b[n], rtol=1e-5, atol=1e-7) for n in a)
+    assert all(np.allclose(a[n], c[n], rtol=1e-5, atol=1e-7) for n in a)
+    assert a["loss"][0] > 0 and np.abs(a["grads"]).max() > 1e-6          # a real step: a loss and gradients
+
+
 def test_bench_self_launches_two_gloo_ranks():
     """--gpus 2 without WORLD_SIZE: bench.py starts 2 ranks itself (torch.distributed.run child) and rank 0
     prints the one JSON line with n_gpus 2."""

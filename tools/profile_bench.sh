@@ -11,7 +11,7 @@ mkdir -p "$out"
 cd "$out" || exit 1
 export TMPDIR=/tmp AVSE_PROFILE_MARK=${MARK:-1}
 timeout -k 10 700 rocprofv3 --kernel-trace --stats --output-format csv -d . -o run -- \
-    python "$root/bench.py" --steps "$steps" --no-cpu-baseline --no-roofline-hip --secondary "" "$@" > bench.log 2>&1
+    python "$root/bench.py" --steps "$steps" --full --no-cpu-baseline --no-roofline-hip --secondary "" "$@" > bench.log 2>&1
 rc=$?
 [ $rc -eq 0 ] && python "$root/tools/ktrace_window.py" run_kernel_trace.csv "$steps" window_stats.csv \
     post_window_stats.csv roofline_window_stats.csv
