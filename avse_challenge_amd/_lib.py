@@ -177,6 +177,7 @@ SIGNATURES = {
     "avse_split16_known": (c_i32, [c_i64, c_vp, c_vp, c_vp, c_vp]),
     "avse_dconv_wprep": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp]),
     "avse_dconv_fwd": (c_i32, [c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "avse_dconv_wprep2": (c_i32, [c_vp] * 6),
     "avse_dconv_wgrad16_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64]),
     "avse_dconv_wgrad16": (c_i32, [c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "avse_conv1_fwd": (c_i32, [c_i64] * 3 + [c_vp] * 5),

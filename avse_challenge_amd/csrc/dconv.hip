@@ -596,6 +596,43 @@ __global__ __launch_bounds__(1024) void wprep_kernel(const float* w, int transpo
     }
 }
 
+// The same images from one launch of NSTG workgroups per orientation (blockIdx.x = orientation * NSTG + stage): every
+// workgroup recomputes max |w| from the 400-KB tensor (L2-resident after the first) and writes its own stage's 20 KB;
+// orientation 1 is the transposed image under the same max.  The max is a maximum of the same values and the split
+// the same expression, so the bytes equal wprep_kernel's.  Workgroup 0 publishes the max bits (mb0[1], mb1[1]).
+__global__ __launch_bounds__(1024) void wprep2_kernel(const float* w, uint32_t* mb0, uint32_t* mb1, uint16_t* wq0,
+                                                      uint16_t* wq1) {
+    __shared__ uint32_t red[16];
+    constexpr int TOT = C * C * KS * KS, PER = KS * C * 16;       // elements per stage
+    float m = 0.f;
+    for (int i = threadIdx.x; i < TOT; i += 1024) m = fmaxf(m, fabsf(w[i]));
+    uint32_t b = __float_as_uint(m);
+    for (int o = 32; o >= 1; o >>= 1) b = max(b, (uint32_t)__shfl_xor((int)b, o, 64));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = b;
+    __syncthreads();
+    b = 0;
+    for (int k = 0; k < 16; ++k) b = max(b, red[k]);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        mb0[1] = b;
+        if (mb1) mb1[1] = b;
+    }
+    const float sc = __builtin_ldexpf(1.f, split_exp(b));
+    const int transposed = blockIdx.x / NSTG, s = blockIdx.x % NSTG;
+    uint16_t* wq = transposed ? wq1 : wq0;
+    const int kh = s / NQ, q = s % NQ;
+    for (int e = threadIdx.x; e < PER; e += 1024) {
+        const int c = e % 16, o = (e / 16) % C, kw = e / (16 * C);
+        const int i = q * 16 + c;
+        const float v = transposed ? w[((i * C + o) * KS + (KS - 1 - kh)) * KS + (KS - 1 - kw)]
+                                   : w[((o * C + i) * KS + kh) * KS + kw];
+        const float sv = v * sc;
+        const _Float16 h = (_Float16)sv, l = (_Float16)(sv - (float)h);
+        const int64_t row = ((int64_t)s * KS + kw) * C + o;
+        wq[row * 32 + c] = __builtin_bit_cast(uint16_t, h);
+        wq[row * 32 + 16 + c] = __builtin_bit_cast(uint16_t, l);
+    }
+}
+
 }  // namespace dcf
 }  // namespace avse
 
@@ -638,6 +675,15 @@ int avse_dconv_wprep(const float* w, int32_t transposed, void* wq, uint32_t* max
     if (!w || !wq || !maxbits) return AVSE_EINVAL;
     hipLaunchKernelGGL(wprep_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, w, transposed, maxbits,
                        reinterpret_cast<uint16_t*>(wq));
+    AVSE_CHECK_LAUNCH();
+    return AVSE_OK;
+}
+
+int avse_dconv_wprep2(const float* w, void* wq, void* wq_t, uint32_t* maxbits, uint32_t* maxbits_t,
+                      avse_stream_t stream) {
+    if (!w || !wq || !maxbits || (wq_t == nullptr) != (maxbits_t == nullptr)) return AVSE_EINVAL;
+    hipLaunchKernelGGL(wprep2_kernel, dim3(wq_t ? 2 * NSTG : NSTG), dim3(1024), 0, (hipStream_t)stream, w, maxbits,
+                       maxbits_t, reinterpret_cast<uint16_t*>(wq), reinterpret_cast<uint16_t*>(wq_t));
     AVSE_CHECK_LAUNCH();
     return AVSE_OK;
 }

@@ -537,11 +537,13 @@ using namespace avse::pg;
 // whose rows are 16-B aligned for the GEMM's DMA): hi = fp16(x 2^e), lo = fp16(x 2^e - hi) with max |x| 2^e in
 // [2^14, 2^15) (dconv.hip's split, the same 22 significant bits); the planes' padding is not written.
 // Two streaming passes (max, then split): a workgroup takes rpb consecutive rows, float4 accesses when the rows are
-// 16-B aligned (VEC), the row's last c % 4 elements one by one; 4 accesses in flight per thread either way.
+// 16-B aligned (VEC), the row's last c % 4 elements one by one; 4 accesses in flight per thread either way.  The max
+// pass of a contiguous x ignores the rows altogether (planes_absmax_flat_kernel).
 struct PlanesArgs {
     const float* x;
     int64_t rows, r, c, bs, rs, hbs, hrs;
     int rpb;
+    int tpr;                     // absmax row walk: threads per row (a power of two <= AM_NT), AM_NT / tpr rows in flight
     uint32_t* maxbits;
     _Float16* hi;
     _Float16* lo;
@@ -557,35 +559,8 @@ __device__ inline int64_t planes_out_off(const PlanesArgs& a, int64_t row) {
 // blocks cost 6.8 ms for a C3 activation, profiles/r05i_gemm_f32s_probe.jsonl; 2048 per call cost ~30 us of a 65 MB
 // pass), while 16 waves per CU keep enough loads in flight
 constexpr int AM_NT = 1024, AM_GRID = 256;
-template <bool VEC>
-__global__ __launch_bounds__(AM_NT) void planes_absmax_kernel(PlanesArgs a, int64_t nrb) {
-    __shared__ uint32_t red[AM_NT / 64];
-    float m = 0.f;
-    const int64_t c4 = VEC ? a.c / 4 : 0;
-    for (int64_t rb = blockIdx.x; rb < nrb; rb += gridDim.x)
-    for (int rr = 0; rr < a.rpb; ++rr) {
-        const int64_t row = rb * a.rpb + rr;
-        if (row >= a.rows) break;
-        const float* xr = a.x + planes_row_off(a, row);
-        if constexpr (VEC) {
-            for (int64_t j0 = threadIdx.x; j0 < c4; j0 += 4 * AM_NT) {
-                float4 v[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-                    v[u] = j0 + u * AM_NT < c4 ? reinterpret_cast<const float4*>(xr)[j0 + u * AM_NT] : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-                    m = fmaxf(m, fmaxf(fmaxf(fabsf(v[u].x), fabsf(v[u].y)), fmaxf(fabsf(v[u].z), fabsf(v[u].w))));
-            }
-        }
-        for (int64_t i0 = 4 * c4 + threadIdx.x; i0 < a.c; i0 += 4 * AM_NT) {
-            float v[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) v[u] = i0 + u * AM_NT < a.c ? xr[i0 + u * AM_NT] : 0.f;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) m = fmaxf(m, fabsf(v[u]));
-        }
-    }
+
+__device__ inline void absmax_publish(float m, uint32_t* red, uint32_t* maxbits) {
     uint32_t v = __float_as_uint(m);
     for (int o = 32; o >= 1; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o, 64));
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
@@ -593,8 +568,62 @@ __global__ __launch_bounds__(AM_NT) void planes_absmax_kernel(PlanesArgs a, int6
     if (threadIdx.x == 0) {
         for (int k = 1; k < AM_NT / 64; ++k) v = max(v, red[k]);
         v = max(v, red[0]);
-        if (v) atomicMax(a.maxbits, v);
+        if (v) atomicMax(maxbits, v);
     }
+}
+
+// the row walk (strided or padded x): tpr threads take a row, so AM_NT / tpr of the workgroup's rpb rows are in flight
+// at once (c = 64 floats left 16 of 1024 threads busy on one row at a time)
+template <bool VEC>
+__global__ __launch_bounds__(AM_NT) void planes_absmax_kernel(PlanesArgs a, int64_t nrb) {
+    __shared__ uint32_t red[AM_NT / 64];
+    float m = 0.f;
+    const int64_t c4 = VEC ? a.c / 4 : 0;
+    const int tpr = a.tpr, sub = threadIdx.x / tpr, tc = threadIdx.x % tpr, nsub = AM_NT / tpr;
+    for (int64_t rb = blockIdx.x; rb < nrb; rb += gridDim.x)
+    for (int rr = sub; rr < a.rpb; rr += nsub) {
+        const int64_t row = rb * a.rpb + rr;
+        if (row >= a.rows) break;
+        const float* xr = a.x + planes_row_off(a, row);
+        if constexpr (VEC) {
+            for (int64_t j0 = tc; j0 < c4; j0 += 4 * tpr) {
+                float4 v[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+                    v[u] = j0 + u * tpr < c4 ? reinterpret_cast<const float4*>(xr)[j0 + u * tpr] : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+                    m = fmaxf(m, fmaxf(fmaxf(fabsf(v[u].x), fabsf(v[u].y)), fmaxf(fabsf(v[u].z), fabsf(v[u].w))));
+            }
+        }
+        for (int64_t i0 = 4 * c4 + tc; i0 < a.c; i0 += 4 * tpr) {
+            float v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) v[u] = i0 + u * tpr < a.c ? xr[i0 + u * tpr] : 0.f;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) m = fmaxf(m, fabsf(v[u]));
+        }
+    }
+    absmax_publish(m, red, a.maxbits);
+}
+
+// contiguous x (16-B aligned): the flat array of n4 float4, grid-strided with 4 loads in flight per thread, whatever the
+// row length; the last n % 4 elements go to workgroup 0
+__global__ __launch_bounds__(AM_NT) void planes_absmax_flat_kernel(const float* x, int64_t n, uint32_t* maxbits) {
+    __shared__ uint32_t red[AM_NT / 64];
+    float m = 0.f;
+    const int64_t n4 = n / 4, stride = (int64_t)gridDim.x * AM_NT;
+    const float4* x4 = reinterpret_cast<const float4*>(x);
+    for (int64_t i0 = blockIdx.x * (int64_t)AM_NT + threadIdx.x; i0 < n4; i0 += 4 * stride) {
+        float4 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = i0 + u * stride < n4 ? x4[i0 + u * stride] : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            m = fmaxf(m, fmaxf(fmaxf(fabsf(v[u].x), fabsf(v[u].y)), fmaxf(fabsf(v[u].z), fabsf(v[u].w))));
+    }
+    if (blockIdx.x == 0 && 4 * n4 + threadIdx.x < n) m = fmaxf(m, fabsf(x[4 * n4 + threadIdx.x]));
+    absmax_publish(m, red, maxbits);
 }
 
 __device__ inline uint32_t split_pair(float x0, float x1, float sc, uint32_t& lo) {
@@ -899,6 +928,7 @@ static int split16_planes_impl(int64_t b, int64_t r, int64_t c, const float* x, 
     a.maxbits = maxbits;
     a.hi = (_Float16*)hi;
     a.lo = (_Float16*)lo;
+    a.tpr = AM_NT;
     // rows per workgroup: ~1024 float4 of work each
     const int64_t c4 = (c + 3) / 4;
     a.rpb = (int)std::max<int64_t>(1, std::min<int64_t>(1024 / std::max<int64_t>(c4, 1), 64));
@@ -911,33 +941,24 @@ static int split16_planes_impl(int64_t b, int64_t r, int64_t c, const float* x, 
     const bool pad = hvec && (h_rs != x_rs || (b > 1 && h_bs != x_bs) || (zero_pad && h_rs > c));
     if (!known) {
         const int64_t n = b * r * c;
-        if (xvec) {
-            hipLaunchKernelGGL(planes_absmax_kernel<true>, dim3((unsigned)std::min<int64_t>(blocks, AM_GRID)), dim3(AM_NT), 0,
-                               st, a, blocks);
-            AVSE_CHECK_LAUNCH();
-        } else if (x_rs == c && (b == 1 || x_bs == r * c) && ((uintptr_t)x % 16 == 0) && n >= 4096) {
-            // contiguous x whose rows are not 16-B aligned: the flat array in 4096-element rows (float4), the tail as
-            // one more row
-            PlanesArgs f = a;
-            f.rows = f.r = n / 4096;
-            f.c = f.rs = 4096;
-            f.bs = 0;
-            f.rpb = 1;
-            hipLaunchKernelGGL(planes_absmax_kernel<true>, dim3((unsigned)std::min<int64_t>(f.rows, AM_GRID)), dim3(AM_NT), 0,
-                               st, f, f.rows);
-            AVSE_CHECK_LAUNCH();
-            if (n % 4096) {
-                f.x = x + f.rows * 4096;
-                f.rows = f.r = 1;
-                f.c = f.rs = n % 4096;
-                hipLaunchKernelGGL(planes_absmax_kernel<false>, dim3(1), dim3(AM_NT), 0, st, f, (int64_t)1);
-                AVSE_CHECK_LAUNCH();
-            }
+        if (x_rs == c && (b == 1 || x_bs == r * c) && ((uintptr_t)x % 16 == 0)) {
+            // contiguous x: one flat pass, every thread busy whatever the row length (rows of c = 64 .. 512 floats, the
+            // (N P, c) operands of the shortcut weight gradients, left most of the row walk's threads idle)
+            const int64_t wgs = std::max<int64_t>(1, std::min<int64_t>(AM_GRID, (n / 4 + AM_NT - 1) / AM_NT));
+            hipLaunchKernelGGL(planes_absmax_flat_kernel, dim3((unsigned)wgs), dim3(AM_NT), 0, st, x, n, maxbits);
         } else {
-            hipLaunchKernelGGL(planes_absmax_kernel<false>, dim3((unsigned)std::min<int64_t>(blocks, AM_GRID)), dim3(AM_NT), 0,
-                               st, a, blocks);
-            AVSE_CHECK_LAUNCH();
+            // threads per row: the row's float4 (VEC) or float count, as a power of two
+            const int64_t per_row = xvec ? c4 : c;
+            a.tpr = 1;
+            while (a.tpr < AM_NT && a.tpr < per_row) a.tpr <<= 1;
+            if (xvec)
+                hipLaunchKernelGGL(planes_absmax_kernel<true>, dim3((unsigned)std::min<int64_t>(blocks, AM_GRID)),
+                                   dim3(AM_NT), 0, st, a, blocks);
+            else
+                hipLaunchKernelGGL(planes_absmax_kernel<false>, dim3((unsigned)std::min<int64_t>(blocks, AM_GRID)),
+                                   dim3(AM_NT), 0, st, a, blocks);
         }
+        AVSE_CHECK_LAUNCH();
     }
     if (pad) {
         PlanesArgs p2 = a;

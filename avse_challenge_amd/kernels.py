@@ -582,11 +582,27 @@ def dconv_wprep(w, transposed, maxbits):
     return wq
 
 
-def dconv_fwd(x, w, dilation, bias=None, transposed=False, split=None):
+def dconv_wprep2(w, maxbits, maxbits_t=None):
+    """W (64, 64, 5, 5) fp32 -> (wq, wq_t): dconv.hip's split weight image and, when maxbits_t (the input gradient's
+    (2,) int32 pair) is given, the transposed image too (else None), from one launch of one workgroup per stage and
+    orientation; max |w| goes into maxbits[1] and maxbits_t[1].  The bytes are dconv_wprep's."""
+    _need_gpu(w)
+    L = _lib.lib()
+    nb = int(L.avse_dconv_wprep_bytes())
+    wq = torch.empty(nb, device=w.device, dtype=torch.uint8)
+    wq_t = torch.empty(nb, device=w.device, dtype=torch.uint8) if maxbits_t is not None else None
+    check(L.avse_dconv_wprep2(ptr(w.float().contiguous()), ptr(wq), ptr(wq_t) if wq_t is not None else None,
+                              ptr(maxbits), ptr(maxbits_t) if maxbits_t is not None else None, stream_ptr(w.device)),
+          "avse_dconv_wprep2")
+    return wq, wq_t
+
+
+def dconv_fwd(x, w, dilation, bias=None, transposed=False, split=None, wq=None):
     """conv2d(x, w, bias, padding=2d, dilation=d) for the 64 -> 64 5x5 AudioFeatNet convs on csrc/dconv.hip (fp16x3
     split MFMA, fp32-accurate); transposed=True: the input gradient conv_transpose(x = dY, w).  x (N, 64, H, W) fp32
     (its shape only, when ``split`` = (xq, maxbits) from split16 is given: maxbits[1] is then overwritten with W's);
-    returns (N, 64, H, W) in channels-last memory."""
+    returns (N, 64, H, W) in channels-last memory.  wq: the weight image of this orientation from dconv_wprep2, whose
+    max is then already in maxbits[1] (w is not read)."""
     _need_gpu(x, w, bias)
     if not dconv_split_ok(x, dilation) or tuple(w.shape) != (64, 64, 5, 5):
         raise RuntimeError(f"dconv_fwd: unsupported shape {tuple(x.shape)} / {tuple(w.shape)} dilation {dilation}")
@@ -596,7 +612,8 @@ def dconv_fwd(x, w, dilation, bias=None, transposed=False, split=None):
         xq = split16(x, maxbits)
     else:
         xq, maxbits = split
-    wq = dconv_wprep(w, transposed, maxbits)
+    if wq is None:
+        wq = dconv_wprep(w, transposed, maxbits)
     y = torch.empty((N, 64, H, W), device=x.device, dtype=torch.float32, memory_format=torch.channels_last)
     tap = _tap_begin("avse_dconv_fwd", x.device)
     check(_lib.lib().avse_dconv_fwd(N, H, W, dilation, ptr(xq), ptr(wq), ptr(maxbits),

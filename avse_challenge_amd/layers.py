@@ -235,8 +235,17 @@ class _DilatedConvFn(torch.autograd.Function):
             # the fp16 hi / lo split of x is made once and kept for the weight gradient in place of x (same bytes)
             mb = torch.empty(2, device=x.device, dtype=torch.int32)
             xq = K.split16(x, mb)
-            y = K.dconv_fwd(x, w, dilation, b if add_bias else None, split=(xq, mb))
-            ctx.save_for_backward(xq, mb, w)
+            # the weights do not change between this forward and its backward: when an input gradient will be asked
+            # for, the one weight-preparation launch also writes the transposed image (and max |w| into the backward's
+            # max pair mbd), kept for the backward
+            mbd = torch.empty(2, device=x.device, dtype=torch.int32) if ctx.needs_input_grad[0] else None
+            wq, wq_t = K.dconv_wprep2(w, mb, mbd)
+            y = K.dconv_fwd(x, w, dilation, b if add_bias else None, split=(xq, mb), wq=wq)
+            ctx.has_wt = wq_t is not None
+            if ctx.has_wt:
+                ctx.save_for_backward(xq, mb, w, wq_t, mbd)
+            else:
+                ctx.save_for_backward(xq, mb, w)
             ctx.shape = tuple(x.shape)
             return y
         ctx.save_for_backward(x, w)
@@ -248,11 +257,14 @@ class _DilatedConvFn(torch.autograd.Function):
         d = ctx.dilation
         dx = dw = db = None
         if ctx.split:
-            xq, mb, w = ctx.saved_tensors
-            mbd = torch.empty(2, device=dy.device, dtype=torch.int32)
+            if ctx.has_wt:
+                xq, mb, w, wq_t, mbd = ctx.saved_tensors      # mbd[1] holds max |w| since the forward
+            else:
+                xq, mb, w = ctx.saved_tensors
+                wq_t, mbd = None, torch.empty(2, device=dy.device, dtype=torch.int32)
             dyq = K.split16(dy, mbd)                   # shared by the input and the weight gradient
             if ctx.needs_input_grad[0]:
-                dx = K.dconv_fwd(dy, w, d, transposed=True, split=(dyq, mbd))
+                dx = K.dconv_fwd(dy, w, d, transposed=True, split=(dyq, mbd), wq=wq_t)
             if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
                 dw, db = K.dconv_wgrad16((xq, mb[:1]), (dyq, mbd[:1]), ctx.shape, d, bias_grad=True)
                 dw = dw if ctx.needs_input_grad[1] else None

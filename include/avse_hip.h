@@ -480,6 +480,11 @@ int avse_split16(int64_t n_pix, const float* x, void* xq, uint32_t* maxbits, avs
 /* avse_split16 with max |x| already in maxbits[0] (e.g. avse_bnact_fwd's y_max): the split pass only */
 int avse_split16_known(int64_t n_pix, const float* x, void* xq, const uint32_t* maxbits, avse_stream_t stream);
 int avse_dconv_wprep(const float* w, int32_t transposed, void* wq, uint32_t* maxbits, avse_stream_t stream);
+/* Both images from one launch (one workgroup per stage and orientation): wq as transposed = 0 and, when wq_t is given,
+ * wq_t as transposed = 1, the same bytes as avse_dconv_wprep's; max |w| bits to maxbits[1] and maxbits_t[1] (the
+ * input gradient's pair).  wq_t and maxbits_t are both null or both set. */
+int avse_dconv_wprep2(const float* w, void* wq, void* wq_t, uint32_t* maxbits, uint32_t* maxbits_t,
+                      avse_stream_t stream);
 
 /* 3x3 convolutions of the lip-encoder ResNet trunks (csrc/sconv.hip), replacing
  * nn.Conv2d(ci, co, 3, stride, padding=1, bias=False) of baseline/avse1/utils/resnet.py:9-10 (BasicBlock :26-67)
