@@ -141,6 +141,14 @@ SIGNATURES = {
                                  c_vp, c_vp, c_vp, c_vp, c_vp]),
     "avse_bnact_bwd_q": (c_i32, [c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_vp,
                                  c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "avse_bnact_rows_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64]),
+    # BatchNorm backward from the input-gradient conv's epilogue rows (model.py:199-215, utils/resnet.py:40-67)
+    "avse_bnact_bwd_rows": (c_i32, [c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_vp,
+                                    c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
+    "avse_dconv_bn_rows": (c_i64, [c_i64] * 4),
+    "avse_dconv_dgrad_bn": (c_i32, [c_i64] * 4 + [c_vp] * 8 + [c_i32, c_i32, c_vp, c_vp]),
+    "avse_sconv_bn_rows": (c_i64, [c_i64] * 4),
+    "avse_sconv_dgrad1_bn": (c_i32, [c_i64] * 5 + [c_vp] * 9 + [c_i32, c_vp, c_i32, c_i32, c_vp, c_vp]),
     "avse_prelu_nhwc_fwd": (c_i32, [c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "avse_prelu_nhwc_bwd_workspace_bytes": (c_i64, [c_i64, c_i64]),
     "avse_prelu_nhwc_bwd": (c_i32, [c_i64, c_i64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),

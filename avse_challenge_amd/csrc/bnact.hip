@@ -17,16 +17,18 @@
 // E[x^2] - E[x]^2 does not cancel for large-mean inputs (raw 0..255 lip pixels through Conv3d).
 //
 // HBM traffic per element: forward 4 B (statistics) + 8 B (apply, +4 with a residual); backward 8 B
-// (partials) + 12 B (apply); with a residual 12 + 4 (dres written) and 12.
+// (partials) + 12 B (apply); with a residual 12 + 4 (dres written) and 12.  Where dy comes from a split-fp16
+// input-gradient convolution whose epilogue wrote the per-tile sums (bnact_cols.h, avse_bnact_bwd_rows) the backward's
+// partials pass is not run: 12 B (apply) + 4 B (x, read in the producer's epilogue).
 #include <algorithm>
 
+#include "bnact_cols.h"
 #include "common.h"
 
 namespace avse {
 namespace bnact {
 
 constexpr int THREADS = 256;
-enum { ACT_NONE = 0, ACT_RELU = 1, ACT_PRELU = 2 };
 
 struct Geo {
     int64_t N, CS, S;
@@ -47,44 +49,6 @@ template <> struct vld<4> {
         *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
     }
 };
-
-// per-column constants of the thread's V columns: z = (x - mean) a + b (+ res) -- centred first, as torch does,
-// so large-mean inputs do not lose the low bits of z to a cancelling a x + (beta - mean a) -- act slope, rstd
-// The mean is carried as a float pair (hi + lo): x - hi is exact for x near the mean (Sterbenz), so the
-// centred value keeps its low bits even when |mean| >> std (a ReLU/PReLU mask computed from z would
-// otherwise flip for |z| below a * ulp(mean); torch's CPU kernels centre in double).
-template <int V, int ACT>
-struct ColConst {
-    float a[V], b[V], al[V], mean[V], mlo[V], rstd[V], gam[V];
-    __device__ inline float centred(float v, int k) const { return (v - mean[k]) - mlo[k]; }
-    __device__ inline void load(const Geo& g, int64_t j0, const float* stats, const float* gamma, const float* beta,
-                                const float* alpha, int alpha_n) {
-#pragma unroll
-        for (int k = 0; k < V; ++k) {
-            const int c = (int)((j0 + k) / g.S);
-            mean[k] = stats[4 * c];
-            mlo[k] = stats[4 * c + 1];
-            rstd[k] = stats[4 * c + 2];
-            gam[k] = gamma ? gamma[c] : 1.f;
-            a[k] = gam[k] * rstd[k];
-            b[k] = beta ? beta[c] : 0.f;
-            al[k] = ACT == ACT_PRELU ? alpha[alpha_n > 1 ? c : 0] : 0.f;
-        }
-    }
-};
-
-template <int ACT>
-__device__ inline float act_fwd(float z, float al) {
-    if constexpr (ACT == ACT_RELU) return z > 0.f ? z : 0.f;
-    else if constexpr (ACT == ACT_PRELU) return z > 0.f ? z : al * z;
-    else return z;
-}
-template <int ACT>
-__device__ inline float act_bwd(float z, float g, float al) {
-    if constexpr (ACT == ACT_RELU) return z > 0.f ? g : 0.f;
-    else if constexpr (ACT == ACT_PRELU) return z > 0.f ? g : al * g;
-    else return g;
-}
 
 // Sum NQ per-thread column partials over the workgroup's RPI row offsets (quantity MAXQ, if in range: their max);
 // row offset 0 writes ws[(blockIdx.y * NQ + q) * CS + j].
@@ -321,7 +285,7 @@ __global__ __launch_bounds__(THREADS) void apply_kernel(Geo g, const float* __re
                 float v[V];
                 vld<V>::ld(x + r * g.CS + j0, v);
 #pragma unroll
-                for (int k = 0; k < V; ++k) v[k] = act_fwd<ACT>(fmaf(cc.centred(v[k], k), cc.a[k], cc.b[k]), cc.al[k]);
+                for (int k = 0; k < V; ++k) v[k] = act_fwd<ACT>(cc.preact(v[k], k), cc.al[k]);
                 q_store4(reinterpret_cast<uint16_t*>(y), r, g.CS, j0, v, sc);
             }
         }
@@ -337,7 +301,7 @@ __global__ __launch_bounds__(THREADS) void apply_kernel(Geo g, const float* __re
             if (RES) vld<V>::ld(res + o, rv);
 #pragma unroll
             for (int k = 0; k < V; ++k) {
-                float z = fmaf(cc.centred(v[k], k), cc.a[k], cc.b[k]);
+                float z = cc.preact(v[k], k);
                 if (RES) z += rv[k];
                 v[k] = act_fwd<ACT>(z, cc.al[k]);
                 m = fmaxf(m, fabsf(v[k]));
@@ -376,10 +340,10 @@ __global__ __launch_bounds__(THREADS) void bwd_partial_kernel(Geo g, const float
             if (RES) vld<V>::ld(res + o, rv);
 #pragma unroll
             for (int k = 0; k < V; ++k) {
-                float z = fmaf(cc.centred(v[k], k), cc.a[k], cc.b[k]);
+                float z = cc.preact(v[k], k);
                 if (RES) z += rv[k];
                 dz[k] = act_bwd<ACT>(z, gv[k], cc.al[k]);
-                const float xh = cc.centred(v[k], k) * cc.rstd[k];
+                const float xh = cc.xhat(v[k], k);
                 p[0][k] += dz[k];
                 p[1][k] = fmaf(dz[k], xh, p[1][k]);
                 if (ACT == ACT_PRELU && !(z > 0.f)) p[2][k] = fmaf(gv[k], z, p[2][k]);
@@ -448,11 +412,11 @@ __device__ inline void bwd_apply_cols(const Geo& g, int64_t j0, int ty, const fl
             float gv[V];
             vld<V>::ld(dy + o, gv);
 #pragma unroll
-            for (int k = 0; k < V; ++k) dz[k] = act_bwd<ACT>(fmaf(cc.centred(v[k], k), cc.a[k], cc.b[k]), gv[k], cc.al[k]);
+            for (int k = 0; k < V; ++k) dz[k] = act_bwd<ACT>(cc.preact(v[k], k), gv[k], cc.al[k]);
         }
 #pragma unroll
         for (int k = 0; k < V; ++k) {
-            const float xh = cc.centred(v[k], k) * cc.rstd[k];
+            const float xh = cc.xhat(v[k], k);
             v[k] = cc.a[k] * (dz[k] - k1[k] - xh * k2[k]);
             if constexpr (!QOUT) m = fmaxf(m, fabsf(v[k]));
         }
@@ -674,6 +638,57 @@ int avse_bnact_bwd_q(int64_t N, int64_t C, int64_t S, const float* x, const floa
                      uint32_t* dx_bound, avse_stream_t stream) {
     return bnact_bwd_impl(N, C, S, x, nullptr, dy, stats, gamma, beta, act, alpha, alpha_n, training, (float*)dxq,
                           nullptr, dgamma, dbeta, dalpha_c, workspace, dx_bound, true, (hipStream_t)stream);
+}
+
+// ---- backward from producer-written rows (csrc/bnact_cols.h: the epilogue of the split-fp16 input-gradient
+// convolution that wrote dy also wrote, per pixel tile, one row of the per-channel sums): chan_partial_kernel over
+// `rows` rows in place of the row blocks of bwd_partial_kernel, then bwd_combine and bwd_apply_kernel as ever.
+// workspace: [rows][NQ][C] floats (written by the producer), kbuf (2 C), 16-aligned fp64 per-channel partials.
+static inline int64_t rows_floats(int64_t rows, int64_t C, int64_t nq) { return rows * nq * C; }
+
+int64_t avse_bnact_rows_workspace_bytes(int64_t rows, int64_t C, int64_t nq) {
+    if (rows <= 0 || rows >= (1 << 23) || C <= 0 || C >= (1 << 20) || (nq != 3 && nq != 4)) return 0;
+    return 4 * (rows_floats(rows, C, nq) + 2 * C) + 16 + 8 * C * MAXG * 4;
+}
+
+int avse_bnact_bwd_rows(int64_t N, int64_t C, int64_t rows, const float* x, const float* dy, const float* stats,
+                        const float* gamma, const float* beta, int32_t act, const float* alpha, int32_t alpha_n,
+                        int32_t training, float* dx, float* dgamma, float* dbeta, float* dalpha_c, float* workspace,
+                        uint32_t* dx_max, int32_t q_out, avse_stream_t stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!x || !dy || !stats || !dx || !workspace || !dx_max || (act == ACT_PRELU && (!alpha || !dalpha_c)))
+        return AVSE_EINVAL;
+    if (!shape_ok(N, C, 1) || act < ACT_NONE || act > ACT_PRELU) return AVSE_ESHAPE;
+    if (act == ACT_PRELU && alpha_n != 1 && alpha_n != C) return AVSE_ESHAPE;
+    if (rows <= 0 || rows >= (1 << 23)) return AVSE_ESHAPE;                  // chan_partial_kernel: cnt < 2^23
+    if (C % 4 || !al16(x) || !al16(dy) || !al16(dx) || !al16(workspace)) return AVSE_EALIGN;
+    if (q_out && C % 64) return AVSE_ESHAPE;
+    const int nq = q_out ? 4 : 3;
+    const Geo g = make_geo(N, C, 1, 4);
+    Geo gr = g;
+    gr.nrb = (int)rows;
+    float* kbuf = workspace + rows_floats(rows, C, nq);
+    double* fin = reinterpret_cast<double*>(((uintptr_t)(kbuf + 2 * C) + 15) & ~(uintptr_t)15);
+    const int G = chan_groups(gr);
+    if (q_out)
+        hipLaunchKernelGGL((chan_partial_kernel<4, 3>), dim3((unsigned)C, G), dim3(THREADS), 0, st, gr,
+                           (const float*)workspace, fin, dx_max);
+    else
+        hipLaunchKernelGGL((chan_partial_kernel<3>), dim3((unsigned)C, G), dim3(THREADS), 0, st, gr,
+                           (const float*)workspace, fin, (uint32_t*)nullptr);
+    AVSE_CHECK_LAUNCH();
+    hipLaunchKernelGGL(bwd_combine, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, st, g, (const double*)fin, G,
+                       (int)training, dgamma, dbeta, dalpha_c, kbuf, dx_max, (int)(q_out != 0), stats, gamma);
+    AVSE_CHECK_LAUNCH();
+    const dim3 grid(g.tiles, g.nrb);
+    if (q_out)
+        dispatch_q<BwdApplyQK>::run(act, grid, st, g, x, dy, (const float*)nullptr, stats, gamma, beta, alpha,
+                                   (int)alpha_n, (const float*)kbuf, dx, dx_max);
+    else
+        dispatch<BwdApplyK>::run(4, act, false, grid, st, g, x, dy, (const float*)nullptr, stats, gamma, beta, alpha,
+                                 (int)alpha_n, (const float*)kbuf, dx, dx_max);
+    AVSE_CHECK_LAUNCH();
+    return AVSE_OK;
 }
 
 }  // extern "C"

@@ -33,6 +33,7 @@
 // c ^ ((r >> 2) & 3), so the 16 lanes of a ds_read_b128 group read 16 distinct bank slots.
 #include <algorithm>
 
+#include "bnact_cols.h"
 #include "common.h"
 
 namespace avse {
@@ -112,13 +113,17 @@ struct Args {
     const float* bias;           // (64) or NULL
     float* y;                    // NHWC fp32
     int N, H, W, tiles;          // tiles per image
+    bnact::BnEpi bn;             // EPI launches only (input gradient of a conv whose input is ReLU(BN(bn.x)))
 };
 
 // NW waves, tile = TP = 64 NW raster pixels spanning up to NSEG rows (W >= 256): row segment k of the tile sits at LDS
 // positions S_k .. S_k + n_k + 4 D (its n_k pixels with the 2 D halo each side), S_k = n_0 + .. + n_{k-1} + 4 D k, so
 // output pixel j of segment k reads position j + 4 D k + D kw for tap kw.
 // WGS workgroups per CU: 2 (NW = 4) takes 2 LDS buffers, so that two workgroups fit; 1: 3 buffers where they fit.
-template <int D, int NW, int WGS = 1>
+// EPI (input-gradient launches; 0: none, the forward's code): the tile's BatchNorm-backward partials of
+// y = ReLU(BN(a.bn.x)) with dy = this kernel's output (bnact_cols.h), one row a.bn.rows[workgroup] per tile, NQ = 3
+// (EPI = 1) or 4 (EPI = 2: with max |dz|) quantities.
+template <int D, int NW, int WGS = 1, int EPI = 0>
 __global__ __launch_bounds__(64 * NW, WGS) void fwd_kernel(Args a) {
     constexpr int TPX = 64 * NW, NSEG = NW == 4 ? 2 : 3;
     constexpr int NP = (TPX + 4 * D * NSEG + 15) / 16 * 16;   // staged positions (whole 1-KB DMA pieces)
@@ -252,8 +257,7 @@ __global__ __launch_bounds__(64 * NW, WGS) void fwd_kernel(Args a) {
 
     // epilogue: acc[i][j] register 4 g + e = pixel 64 wave + 32 i + 8 g + 4 (lane >> 5) + e, channel 32 j + (lane & 31)
     const float scale = __builtin_ldexpf(1.f, -(split_exp(a.maxbits[0]) + split_exp(a.maxbits[1])));
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
+    auto store = [&](int j) {
         const int o = 32 * j + (lane & 31);
         const float bv = a.bias ? a.bias[o] : 0.f;
 #pragma unroll
@@ -263,8 +267,23 @@ __global__ __launch_bounds__(64 * NW, WGS) void fwd_kernel(Args a) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int p = p0 + 64 * wave + 32 * i + 8 * g + 4 * (lane >> 5) + e;
-                    if (p < HW) a.y[((int64_t)n * HW + p) * C + o] = acc[i][j][4 * g + e] * scale + bv;
+                    const float v = acc[i][j][4 * g + e] * scale + bv;
+                    if constexpr (EPI != 0) acc[i][j][4 * g + e] = v;      // the stored value, kept for the partials
+                    if (p < HW) a.y[((int64_t)n * HW + p) * C + o] = v;
                 }
+    };
+    if constexpr (EPI == 0) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) store(j);
+    } else {
+        constexpr int ENQ = EPI == 2 ? 4 : 3;
+        float* part = reinterpret_cast<float*>(lds);      // every wave is past its last fragment read (lgkmcnt(0) or
+        __syncthreads();                                  // the MFMAs' operands) before the staging ring is reused
+        bnact::bn_epi_wave<bnact::ACT_RELU, EPI == 2>(
+            a.bn, [&](int i, int j, int r) { return acc[i][j][r]; }, store, (int64_t)n * HW + p0 + 64 * wave,
+            (int64_t)(n + 1) * HW, 0, C, lane, part + wave * ENQ * 64);
+        __syncthreads();
+        bnact::bn_epi_row<EPI == 2>(a.bn, part, NW, 1, (int64_t)bid, 0, C);
     }
 }
 
@@ -728,8 +747,42 @@ int avse_dconv_wgrad16(int64_t N, int64_t H, int64_t W, int64_t dil, const void*
     return AVSE_OK;
 }
 
+static inline int dcf_nw(int64_t dil) { return dil <= 8 ? 4 : 8; }
+
+int64_t avse_dconv_bn_rows(int64_t N, int64_t H, int64_t W, int64_t dil) {
+    if (N <= 0 || H <= 0 || W < 256) return 0;
+    return N * ((H * W + 64 * dcf_nw(dil) - 1) / (64 * dcf_nw(dil)));
+}
+
+static int dconv_launch(int64_t N, int64_t H, int64_t W, int64_t dil, const void* xq, const void* wq,
+                        const uint32_t* maxbits, const float* bias, float* y, const avse::bnact::BnEpi* bn, int epi,
+                        avse_stream_t stream);
+
 int avse_dconv_fwd(int64_t N, int64_t H, int64_t W, int64_t dil, const void* xq, const void* wq,
                    const uint32_t* maxbits, const float* bias, float* y, avse_stream_t stream) {
+    return dconv_launch(N, H, W, dil, xq, wq, maxbits, bias, y, nullptr, 0, stream);
+}
+
+int avse_dconv_dgrad_bn(int64_t N, int64_t H, int64_t W, int64_t dil, const void* dyq, const void* wq_t,
+                        const uint32_t* maxbits, float* dx, const float* bn_x, const float* bn_stats,
+                        const float* gamma, const float* beta, int32_t act, int32_t want_max, float* rows,
+                        avse_stream_t stream) {
+    if (!bn_x || !bn_stats || !rows) return AVSE_EINVAL;
+    if (act != avse::bnact::ACT_RELU) return AVSE_ESHAPE;
+    avse::bnact::BnEpi bn;
+    bn.x = bn_x;
+    bn.stats = bn_stats;
+    bn.gamma = gamma;
+    bn.beta = beta;
+    bn.alpha = nullptr;
+    bn.alpha_n = 0;
+    bn.rows = rows;
+    return dconv_launch(N, H, W, dil, dyq, wq_t, maxbits, nullptr, dx, &bn, want_max ? 2 : 1, stream);
+}
+
+static int dconv_launch(int64_t N, int64_t H, int64_t W, int64_t dil, const void* xq, const void* wq,
+                        const uint32_t* maxbits, const float* bias, float* y, const avse::bnact::BnEpi* bn, int epi,
+                        avse_stream_t stream) {
     if (!xq || !wq || !maxbits || !y) return AVSE_EINVAL;
     if (N <= 0 || H <= 0 || W < 256 || (dil != 2 && dil != 4 && dil != 8 && dil != 16)) return AVSE_ESHAPE;
     if (N * H * W * 256 >= (1LL << 31) - 1024) return AVSE_ESHAPE;       // 32-bit byte offsets into the split input
@@ -746,16 +799,23 @@ int avse_dconv_fwd(int64_t N, int64_t H, int64_t W, int64_t dil, const void* xq,
     // workgroups' barriers and DMA phases interleave, 1.61 vs 1.69 ms per launch at C2 against one 8-wave 512-pixel
     // workgroup per CU (profiles/r06g_dconv_fwd_ab.jsonl; one 4-wave workgroup per CU with 3 buffers measured slower in
     // round 5).  d = 16: the 4-wave tile's 4d halos need 89 KB per workgroup, so it keeps the 8-wave form.
-    const int nw = dil <= 8 ? 4 : 8;
+    const int nw = dcf_nw(dil);
+    if (bn) a.bn = *bn;
+    else a.bn = avse::bnact::BnEpi{nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr};
     a.tiles = (int)((H * W + 64 * nw - 1) / (64 * nw));
     const dim3 grid((unsigned)(N * a.tiles)), block(64 * nw);
     hipStream_t st = (hipStream_t)stream;
-    switch (dil) {
-        case 2: hipLaunchKernelGGL((fwd_kernel<2, 4, 2>), grid, block, 0, st, a); break;
-        case 4: hipLaunchKernelGGL((fwd_kernel<4, 4, 2>), grid, block, 0, st, a); break;
-        case 8: hipLaunchKernelGGL((fwd_kernel<8, 4, 2>), grid, block, 0, st, a); break;
-        default: hipLaunchKernelGGL((fwd_kernel<16, 8>), grid, block, 0, st, a); break;
+#define AVSE_DCF_CASES(E)                                                                           \
+    switch (dil) {                                                                                  \
+        case 2: hipLaunchKernelGGL((fwd_kernel<2, 4, 2, E>), grid, block, 0, st, a); break;         \
+        case 4: hipLaunchKernelGGL((fwd_kernel<4, 4, 2, E>), grid, block, 0, st, a); break;         \
+        case 8: hipLaunchKernelGGL((fwd_kernel<8, 4, 2, E>), grid, block, 0, st, a); break;         \
+        default: hipLaunchKernelGGL((fwd_kernel<16, 8, 1, E>), grid, block, 0, st, a); break;       \
     }
+    if (epi == 0) { AVSE_DCF_CASES(0) }
+    else if (epi == 1) { AVSE_DCF_CASES(1) }
+    else { AVSE_DCF_CASES(2) }
+#undef AVSE_DCF_CASES
     AVSE_CHECK_LAUNCH();
     return AVSE_OK;
 }

@@ -26,6 +26,7 @@
 // products = 36 MFMAs.  Two LDS buffers, the next stage issued right after the barrier that frees its buffer.
 #include <algorithm>
 
+#include "bnact_cols.h"
 #include "common.h"
 
 namespace avse {
@@ -92,9 +93,13 @@ struct FArgs {
     int N, Hi, Wi, Ci, Ho, Wo, Co;
     int tiles_n;               // Co / TN
     int RS, npos;              // staged segment length, positions per stage (multiple of 16, <= NPOS_MAX)
+    bnact::BnEpi bn;           // EPI launches only (input gradient of a conv whose input is PReLU(BN(bn.x)))
 };
 
-template <int S, int TN>
+// EPI (stride-1 input-gradient launches; 0: none, the forward's code): the tile's BatchNorm-backward partials of
+// y = PReLU(BN(a.bn.x)) with dy = this kernel's output (bnact_cols.h), one row of a.bn.rows per pixel tile (its TN
+// channels x NQ), NQ = 3 (EPI = 1) or 4 (EPI = 2: with max |dz|).
+template <int S, int TN, int EPI = 0>
 __global__ __launch_bounds__(512, 1) void fwd_kernel(FArgs a) {
     constexpr int WAVES = 8, WN = TN / 64, WM = WAVES / WN, TM = 64 * WM;
     constexpr int WIMG = 3 * TN * ROWB;
@@ -219,8 +224,7 @@ __global__ __launch_bounds__(512, 1) void fwd_kernel(FArgs a) {
     // epilogue: acc[i][j] register 4 g + e = pixel p0 + 64 wm + 32 i + 8 g + 4 (lane >> 5) + e, channel
     // o0 + 64 wn + 32 j + (lane & 31): 32 lanes write 128 contiguous bytes of one pixel
     const float scale = __builtin_ldexpf(1.f, -(split_exp(*a.xmax) + split_exp(*a.wmax)));
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
+    auto store = [&](int j) {
         const int o = o0 + 64 * wn + 32 * j + (lane & 31);
 #pragma unroll
         for (int i = 0; i < 2; ++i)
@@ -229,8 +233,23 @@ __global__ __launch_bounds__(512, 1) void fwd_kernel(FArgs a) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int p = p0 + 64 * wm + 32 * i + 8 * g + 4 * (lane >> 5) + e;
-                    if (p < NHWo) a.y[(int64_t)p * a.Co + o] = acc[i][j][4 * g + e] * scale;
+                    const float v = acc[i][j][4 * g + e] * scale;
+                    if constexpr (EPI != 0) acc[i][j][4 * g + e] = v;      // the stored value, kept for the partials
+                    if (p < NHWo) a.y[(int64_t)p * a.Co + o] = v;
                 }
+    };
+    if constexpr (EPI == 0) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) store(j);
+    } else {
+        constexpr int ENQ = EPI == 2 ? 4 : 3;
+        float* part = reinterpret_cast<float*>(lds);      // the staging buffers are free: no DMA in flight, and after
+        __syncthreads();                                  // the barrier every wave is past its last fragment read
+        bnact::bn_epi_wave<bnact::ACT_PRELU, EPI == 2>(
+            a.bn, [&](int i, int j, int r) { return acc[i][j][r]; }, store, (int64_t)p0 + 64 * wm, (int64_t)NHWo,
+            o0 + 64 * wn, a.Co, lane, part + wave * ENQ * 64);
+        __syncthreads();
+        bnact::bn_epi_row<EPI == 2>(a.bn, part, WM, WN, (int64_t)tm, o0, a.Co);
     }
 }
 
@@ -839,8 +858,41 @@ int avse_sconv_dgrad2(int64_t N, int64_t Hi, int64_t Wi, int64_t ci, int64_t co,
     return AVSE_OK;
 }
 
+static int sconv_launch(int64_t N, int64_t Hi, int64_t Wi, int64_t ci, int64_t co, int64_t stride, const void* xq,
+                        const uint32_t* xmax, const void* wq, const uint32_t* wmax, float* y,
+                        const avse::bnact::BnEpi* bn, int epi, avse_stream_t stream);
+
 int avse_sconv_fwd(int64_t N, int64_t Hi, int64_t Wi, int64_t ci, int64_t co, int64_t stride, const void* xq,
                    const uint32_t* xmax, const void* wq, const uint32_t* wmax, float* y, avse_stream_t stream) {
+    return sconv_launch(N, Hi, Wi, ci, co, stride, xq, xmax, wq, wmax, y, nullptr, 0, stream);
+}
+
+int64_t avse_sconv_bn_rows(int64_t N, int64_t H, int64_t W, int64_t co) {
+    if (N <= 0 || H <= 0 || W <= 0 || co <= 0 || co % 64) return 0;
+    const int64_t TM = co % 128 ? 512 : 256;
+    return (N * H * W + TM - 1) / TM;
+}
+
+int avse_sconv_dgrad1_bn(int64_t N, int64_t H, int64_t W, int64_t ci, int64_t co, const void* dyq,
+                         const uint32_t* dymax, const void* wq_t, const uint32_t* wmax, float* dx, const float* bn_x,
+                         const float* bn_stats, const float* gamma, const float* beta, int32_t act, const float* alpha,
+                         int32_t alpha_n, int32_t want_max, float* rows, avse_stream_t stream) {
+    if (!bn_x || !bn_stats || !rows || !alpha) return AVSE_EINVAL;
+    if (act != avse::bnact::ACT_PRELU || (alpha_n != 1 && alpha_n != co)) return AVSE_ESHAPE;
+    avse::bnact::BnEpi bn;
+    bn.x = bn_x;
+    bn.stats = bn_stats;
+    bn.gamma = gamma;
+    bn.beta = beta;
+    bn.alpha = alpha;
+    bn.alpha_n = alpha_n;
+    bn.rows = rows;
+    return sconv_launch(N, H, W, ci, co, 1, dyq, dymax, wq_t, wmax, dx, &bn, want_max ? 2 : 1, stream);
+}
+
+static int sconv_launch(int64_t N, int64_t Hi, int64_t Wi, int64_t ci, int64_t co, int64_t stride, const void* xq,
+                        const uint32_t* xmax, const void* wq, const uint32_t* wmax, float* y,
+                        const avse::bnact::BnEpi* bn, int epi, avse_stream_t stream) {
     if (!xq || !xmax || !wq || !wmax || !y) return AVSE_EINVAL;
     if (N <= 0 || Hi <= 0 || Wi <= 0 || ci <= 0 || co <= 0 || ci % 64 || co % 64 || (stride != 1 && stride != 2))
         return AVSE_ESHAPE;
@@ -851,6 +903,8 @@ int avse_sconv_fwd(int64_t N, int64_t Hi, int64_t Wi, int64_t ci, int64_t co, in
     a.xmax = xmax;
     a.wmax = wmax;
     a.y = y;
+    if (bn) a.bn = *bn;
+    else a.bn = avse::bnact::BnEpi{nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr};
     a.N = (int)N;
     a.Hi = (int)Hi;
     a.Wi = (int)Wi;
@@ -869,7 +923,12 @@ int avse_sconv_fwd(int64_t N, int64_t Hi, int64_t Wi, int64_t ci, int64_t co, in
     if (tiles >= (1LL << 31)) return AVSE_ESHAPE;
     const dim3 grid((unsigned)tiles), block(512);
     hipStream_t st = (hipStream_t)stream;
-    if (stride == 1) {
+    if (epi != 0) {                                              // stride 1 (avse_sconv_dgrad1_bn)
+        if (TN == 64 && epi == 1) hipLaunchKernelGGL((fwd_kernel<1, 64, 1>), grid, block, 0, st, a);
+        else if (TN == 64) hipLaunchKernelGGL((fwd_kernel<1, 64, 2>), grid, block, 0, st, a);
+        else if (epi == 1) hipLaunchKernelGGL((fwd_kernel<1, 128, 1>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((fwd_kernel<1, 128, 2>), grid, block, 0, st, a);
+    } else if (stride == 1) {
         if (TN == 64) hipLaunchKernelGGL((fwd_kernel<1, 64>), grid, block, 0, st, a);
         else hipLaunchKernelGGL((fwd_kernel<1, 128>), grid, block, 0, st, a);
     } else {

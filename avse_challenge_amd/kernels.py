@@ -623,6 +623,46 @@ def dconv_fwd(x, w, dilation, bias=None, transposed=False, split=None, wq=None):
     return y
 
 
+def _bn_rows_ws(rows, C, q_out, device):
+    """The workspace of bnact_bwd_rows, whose first rows * nq * C floats the producing convolution writes."""
+    nq = 4 if q_out else 3
+    nb = int(_lib.lib().avse_bnact_rows_workspace_bytes(rows, C, nq))
+    if rows <= 0 or nb <= 0:
+        raise RuntimeError(f"bnact rows workspace: unsupported rows {rows} x {C} channels")
+    return torch.empty((nb + 3) // 4, device=device, dtype=torch.float32)
+
+
+def bn_rows_ok(bn_x, gamma, beta, alpha):
+    """True when the fused BatchNorm-backward epilogues take this BatchNorm input: channels-last fp32 (N, C % 64 == 0,
+    H, W), 16-B aligned, fp32 parameters."""
+    return (bn_x.is_cuda and bn_x.dtype == torch.float32 and bn_x.dim() == 4 and bn_x.shape[1] % 64 == 0
+            and not bn_x.is_contiguous() and bn_x.is_contiguous(memory_format=torch.channels_last)
+            and bn_x.data_ptr() % 16 == 0
+            and all(t is None or (t.dtype == torch.float32 and t.is_contiguous()) for t in (gamma, beta, alpha)))
+
+
+def dconv_dgrad_bn(shape, dilation, split, wq_t, bn_x, stats, gamma, beta, act, q_out):
+    """The input gradient dx (shape = (N, 64, H, W), channels-last) of a 64 -> 64 dilated conv whose input was
+    ReLU(BN(bn_x)) -- dconv_fwd(transposed=True) on split = (dyq, maxbits) and the transposed weight image wq_t, bit
+    for bit -- and the rows workspace in which the launch left the BatchNorm backward's per-tile channel sums (with
+    max |dz| when q_out: bnact_bwd_rows(..., q_out) must be given the same value).  -> (dx, rows, ws)."""
+    dyq, maxbits = split
+    _need_gpu(dyq, wq_t, bn_x, stats)
+    N, _, H, W = shape
+    if tuple(bn_x.shape) != tuple(shape) or act != ACT_RELU or not bn_rows_ok(bn_x, gamma, beta, None):
+        raise RuntimeError(f"dconv_dgrad_bn: unsupported BatchNorm input {tuple(bn_x.shape)} act {act}")
+    L = _lib.lib()
+    rows = int(L.avse_dconv_bn_rows(N, H, W, dilation))
+    ws = _bn_rows_ws(rows, 64, q_out, bn_x.device)
+    dx = torch.empty((N, 64, H, W), device=bn_x.device, dtype=torch.float32, memory_format=torch.channels_last)
+    tap = _tap_begin("avse_dconv_fwd", bn_x.device)
+    check(L.avse_dconv_dgrad_bn(N, H, W, dilation, ptr(dyq), ptr(wq_t), ptr(maxbits), ptr(dx), ptr(bn_x), ptr(stats),
+                                _opt(gamma), _opt(beta), int(act), int(bool(q_out)), ptr(ws), stream_ptr(bn_x.device)),
+          "avse_dconv_dgrad_bn")
+    _tap_end(tap)
+    return dx, rows, ws
+
+
 def dconv_wgrad16(xs, dys, shape, dilation, bias_grad=False):
     """dW (64, 64, 5, 5) [and db (64)] of Conv2d(64, 64, 5, padding=2d, dilation=d) from the split input and output
     gradient: xs = (xq, x_maxbits), dys = (dyq, dy_maxbits) from split16 (csrc/dconv.hip, fp16x3 split MFMA);
@@ -791,6 +831,32 @@ def sconv_fwd(xs, xshape, w, stride, transposed=False):
                                     stream_ptr(xq.device)), "avse_sconv_fwd")
     _tap_end(tap)
     return y
+
+
+def sconv_dgrad1_bn(dys, dyshape, w, bn_x, stats, gamma, beta, act, alpha, q_out):
+    """The stride-1 input gradient dx of conv2d(PReLU(BN(bn_x)), w, padding=1) -- sconv_fwd(transposed=True) on
+    dys = (dyq, dymax), bit for bit -- and the rows workspace with the BatchNorm backward's per-tile channel sums (as
+    dconv_dgrad_bn).  -> (dx, rows, ws)."""
+    dyq, dym = dys
+    _need_gpu(dyq, w, bn_x, stats)
+    n, ci, h, wd = dyshape
+    co = w.shape[1]
+    a = alpha
+    if (tuple(bn_x.shape) != (n, co, h, wd) or act != ACT_PRELU or a is None or a.numel() not in (1, co)
+            or not bn_rows_ok(bn_x, gamma, beta, a)):
+        raise RuntimeError(f"sconv_dgrad1_bn: unsupported BatchNorm input {tuple(bn_x.shape)} act {act}")
+    L = _lib.lib()
+    rows = int(L.avse_sconv_bn_rows(n, h, wd, co))
+    ws = _bn_rows_ws(rows, co, q_out, bn_x.device)
+    wm = torch.empty(1, device=w.device, dtype=torch.int32)
+    wq = sconv_wprep(w, True, wm)
+    dx = torch.empty((n, co, h, wd), device=dyq.device, dtype=torch.float32, memory_format=torch.channels_last)
+    tap = _tap_begin("avse_sconv_fwd", dyq.device)
+    check(L.avse_sconv_dgrad1_bn(n, h, wd, ci, co, ptr(dyq), ptr(dym), ptr(wq), ptr(wm), ptr(dx), ptr(bn_x),
+                                 ptr(stats), _opt(gamma), _opt(beta), int(act), ptr(a), a.numel(), int(bool(q_out)),
+                                 ptr(ws), stream_ptr(dyq.device)), "avse_sconv_dgrad1_bn")
+    _tap_end(tap)
+    return dx, rows, ws
 
 
 def sconv_dgrad2_ok(xshape, cout):
@@ -1085,6 +1151,33 @@ def bnact_bwd(x, res, dy, stats, gamma, beta, act, alpha, training, q_out=False)
     if a is not None:
         dalpha = (dalpha_c if a.numel() == C else dalpha_c.sum().reshape(1)).view_as(alpha)
     return dx, dres, dgamma, dbeta, dalpha
+
+
+def bnact_bwd_rows(x, dy, stats, gamma, beta, act, alpha, training, rows, ws, q_out=False):
+    """bnact_bwd without a residual for a channels-last x, from the per-tile channel sums that the convolution which
+    wrote dy left in ws (dconv_dgrad_bn / sconv_dgrad1_bn with the same q_out): no reduction pass over x and dy.
+    -> (dx, None, dgamma, dbeta, dalpha), dx a split-output tensor with q_out."""
+    _need_gpu(x, dy, stats, ws)
+    N, C, S = _bn_view(x)
+    if S != 1 or dy.stride() != x.stride() or dy.dtype != torch.float32:
+        raise RuntimeError("bnact_bwd_rows: channels-last fp32 x and dy of one layout")
+    dx = torch.empty_like(x)
+    dgamma = torch.empty((C,), device=x.device, dtype=torch.float32)
+    dbeta = torch.empty((C,), device=x.device, dtype=torch.float32)
+    a = alpha.float().contiguous() if alpha is not None else None
+    dalpha_c = torch.empty((C,), device=x.device, dtype=torch.float32) if a is not None else None
+    dxmax = torch.empty(1, device=x.device, dtype=torch.int32)
+    check(_lib.lib().avse_bnact_bwd_rows(N, C, int(rows), ptr(x), ptr(dy), ptr(stats), _opt(gamma), _opt(beta),
+                                         int(act), _opt(a), a.numel() if a is not None else 0, int(bool(training)),
+                                         ptr(dx), ptr(dgamma), ptr(dbeta), _opt(dalpha_c), ptr(ws), ptr(dxmax),
+                                         int(bool(q_out)), stream_ptr(x.device)), "avse_bnact_bwd_rows")
+    if q_out:
+        setattr(dx, SPLITQ_ATTR, True)
+    _set_absmax(dx, dxmax)
+    dalpha = None
+    if a is not None:
+        dalpha = (dalpha_c if a.numel() == C else dalpha_c.sum().reshape(1)).view_as(alpha)
+    return dx, None, dgamma, dbeta, dalpha
 
 
 # ------------------------------------------------------------------------ PReLU -> gLN (avse4)

@@ -52,6 +52,40 @@ class PReLU(nn.Module):
         return _PReLUFn.apply(x, self.weight)
 
 
+class _BNPair:
+    """Links a training-mode BatchNorm -> ReLU / PReLU whose split output (q_fwd) feeds ONE split-fp16 convolution to
+    that convolution's autograd node.  The conv's backward launches its input gradient with the BatchNorm-backward
+    epilogue (K.dconv_dgrad_bn / K.sconv_dgrad1_bn: it needs the BatchNorm's input, statistics and parameters, held
+    here) and leaves the per-tile channel sums (`ws`, `rows`) and the gradient tensor it returned (`dy`); the
+    BatchNorm's backward, when it is handed that very tensor unmodified, finishes from the sums (K.bnact_bwd_rows) in
+    place of its reduction pass over x and dy.  Anything else (another consumer added a gradient, a hook replaced it)
+    takes the unfused backward."""
+
+    ATTR = "_avse_bnpair"
+
+    def __init__(self, x, stats, gamma, beta, alpha, act, q_bwd):
+        self.x, self.stats, self.gamma, self.beta, self.alpha, self.act = x, stats, gamma, beta, alpha, act
+        self.q_out = bool(q_bwd) and K._q_ok(x, None)
+        self.clear()
+
+    def clear(self):
+        self.dy = self.dy_version = self.rows = self.ws = None
+
+    def offer(self, dy, rows, ws):
+        self.dy, self.dy_version, self.rows, self.ws = dy, dy._version, rows, ws
+        return dy
+
+    def takes(self, dy):
+        return (self.dy is not None and dy.data_ptr() == self.dy.data_ptr() and dy._version == self.dy_version
+                and dy.shape == self.x.shape and dy.stride() == self.x.stride() and dy.dtype == torch.float32)
+
+    @staticmethod
+    def of(t, act):
+        """The pair a conv input t carries, if its activation is the one the conv's epilogue implements."""
+        pair = getattr(t, _BNPair.ATTR, None)
+        return pair if pair is not None and pair.act == act else None
+
+
 class _BNActFn(torch.autograd.Function):
     """act(BatchNorm(x) [+ res]) in two HBM passes forward and two backward (csrc/bnact.hip)."""
 
@@ -63,13 +97,26 @@ class _BNActFn(torch.autograd.Function):
                                q_out=q_fwd)
         ctx.save_for_backward(x, res, stats, gamma, beta, alpha)
         ctx.act, ctx.training, ctx.q_bwd = act, training, q_bwd
+        ctx.pair = None
+        if (K.is_split_q(y) and training and res is None and act in (K.ACT_RELU, K.ACT_PRELU)
+                and K.bn_rows_ok(x, gamma, beta, alpha)):
+            # the sole consumer is a split-fp16 conv (q_fwd): its input-gradient launch can take this backward's sums
+            ctx.pair = _BNPair(x, stats, gamma, beta, alpha, act, q_bwd)
+            setattr(y, _BNPair.ATTR, ctx.pair)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, res, stats, gamma, beta, alpha = ctx.saved_tensors
-        dx, dres, dgamma, dbeta, dalpha = K.bnact_bwd(x, res, dy, stats, gamma, beta, ctx.act, alpha, ctx.training,
-                                                      q_out=ctx.q_bwd)
+        pair = ctx.pair
+        if pair is not None and pair.takes(dy):
+            dx, dres, dgamma, dbeta, dalpha = K.bnact_bwd_rows(x, dy, stats, gamma, beta, ctx.act, alpha, ctx.training,
+                                                               pair.rows, pair.ws, q_out=pair.q_out)
+        else:
+            dx, dres, dgamma, dbeta, dalpha = K.bnact_bwd(x, res, dy, stats, gamma, beta, ctx.act, alpha, ctx.training,
+                                                          q_out=ctx.q_bwd)
+        if pair is not None:
+            pair.clear()
         return (dx, dgamma if ctx.needs_input_grad[1] else None, dbeta if ctx.needs_input_grad[2] else None,
                 dalpha if ctx.needs_input_grad[3] else None, dres, None, None, None, None, None, None, None, None)
 
@@ -81,7 +128,9 @@ def bn_act(x, bn, act=None, res=None, folded_bias=None, q_fwd=False, q_bwd=False
     q_fwd / q_bwd (round 5): the output / the input gradient as a split-output tensor (kernels.SPLITQ_ATTR) -- ONLY
     when its sole consumer is a split-fp16 convolution: the next conv's forward (q_fwd; DilatedConv2d.q_ok /
     TrunkConv2d.q_ok) or the producing conv's backward (q_bwd; q_ok(..., grad=True)).  Ignored where the kernels
-    cannot produce it (eval forward, residual, NCHW).
+    cannot produce it (eval forward, residual, NCHW).  Where q_fwd takes effect the output also carries a _BNPair: the
+    split conv that consumes it forms this BatchNorm's backward sums in the epilogue of its input-gradient launch, and
+    the backward here then skips its reduction pass over x and dy.
     folded_bias (training mode only): x is a convolution output whose per-channel bias was left out; the result is
     act(bn(x + bias)) — equal to act(bn(x)), the batch statistics shift with the bias — and the running mean takes
     the bias in (momentum * bias)."""
@@ -231,6 +280,7 @@ class _DilatedConvFn(torch.autograd.Function):
         ctx.split = K.dconv_split_ok(x, dilation)
         if K.is_split_q(x) and not ctx.split:
             raise RuntimeError("_DilatedConvFn: a split-output input needs the split path (DilatedConv2d.q_ok)")
+        ctx.bnpair = _BNPair.of(x, K.ACT_RELU) if ctx.split else None
         if ctx.split:
             # the fp16 hi / lo split of x is made once and kept for the weight gradient in place of x (same bytes)
             mb = torch.empty(2, device=x.device, dtype=torch.int32)
@@ -263,7 +313,12 @@ class _DilatedConvFn(torch.autograd.Function):
                 xq, mb, w = ctx.saved_tensors
                 wq_t, mbd = None, torch.empty(2, device=dy.device, dtype=torch.int32)
             dyq = K.split16(dy, mbd)                   # shared by the input and the weight gradient
-            if ctx.needs_input_grad[0]:
+            pair = ctx.bnpair
+            if ctx.needs_input_grad[0] and pair is not None and wq_t is not None:
+                # the input is ReLU(BN(.)) of a paired BatchNorm: the launch also forms that backward's channel sums
+                dx = pair.offer(*K.dconv_dgrad_bn(ctx.shape, d, (dyq, mbd), wq_t, pair.x, pair.stats, pair.gamma,
+                                                  pair.beta, pair.act, pair.q_out))
+            elif ctx.needs_input_grad[0]:
                 dx = K.dconv_fwd(dy, w, d, transposed=True, split=(dyq, mbd), wq=wq_t)
             if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
                 dw, db = K.dconv_wgrad16((xq, mb[:1]), (dyq, mbd[:1]), ctx.shape, d, bias_grad=True)
@@ -620,6 +675,7 @@ class _SConvFn(torch.autograd.Function):
     def forward(ctx, x, w, stride):
         xq, xm = K.split_q(x)                      # the producing BatchNorm pass's max when it comes with x
         ctx.shape, ctx.stride = tuple(x.shape), stride
+        ctx.bnpair = _BNPair.of(x, K.ACT_PRELU) if stride == 1 else None
         ctx.save_for_backward(xq, xm, w)
         return K.sconv_fwd((xq, xm), ctx.shape, w, stride)
 
@@ -630,7 +686,12 @@ class _SConvFn(torch.autograd.Function):
         dyq, dym = K.split_q(dy)                   # (the incoming gradient keeps its producer's max, if any)
         dx = dw = None
         if ctx.needs_input_grad[0]:
-            if s == 1:
+            pair = ctx.bnpair
+            if s == 1 and pair is not None:
+                # the input is PReLU(BN(.)) of a paired BatchNorm: the launch also forms that backward's channel sums
+                dx = pair.offer(*K.sconv_dgrad1_bn((dyq, dym), tuple(dy.shape), w, pair.x, pair.stats, pair.gamma,
+                                                   pair.beta, pair.act, pair.alpha, pair.q_out))
+            elif s == 1:
                 dx = K.sconv_fwd((dyq, dym), tuple(dy.shape), w, 1, transposed=True)
             else:
                 dx = K.sconv_dgrad2((dyq, dym), shape, w)

@@ -299,6 +299,19 @@ int avse_bnact_bwd_q(int64_t N, int64_t C, int64_t S, const float* x, const floa
                      const float* gamma, const float* beta, int32_t act, const float* alpha, int32_t alpha_n,
                      int32_t training, void* dxq, float* dgamma, float* dbeta, float* dalpha_c, float* workspace,
                      uint32_t* dx_bound, avse_stream_t stream);
+/* The backward of a BatchNorm -> ReLU / PReLU whose output feeds ONE split-fp16 convolution (AudioFeatNet bn1..bn4 ->
+ * conv2..conv5, baseline/avse1/model.py:199-215; BasicBlock bn1 -> conv2, baseline/avse1/utils/resnet.py:40-67), from
+ * per-channel sums that the convolution's input-gradient launch formed in its epilogue (avse_dconv_dgrad_bn,
+ * avse_sconv_dgrad1_bn): `rows` rows of [nq][C] floats at the start of `workspace` (nq = 4 with q_out, else 3: sum
+ * dz, sum dz xhat, PReLU slope sum, max |dz|), reduced per channel in fp64, then the apply pass.  No pass over x and
+ * dy for the sums.  Channels-last (S = 1), C % 4 == 0 (q_out: C % 64 == 0), 16-B aligned pointers, rows < 2^23;
+ * workspace of avse_bnact_rows_workspace_bytes(rows, C, nq) (0: not supported).  dx_max as avse_bnact_bwd's (q_out:
+ * the bound, as avse_bnact_bwd_q's dx_bound, dx the split planes). */
+int64_t avse_bnact_rows_workspace_bytes(int64_t rows, int64_t C, int64_t nq);
+int avse_bnact_bwd_rows(int64_t N, int64_t C, int64_t rows, const float* x, const float* dy, const float* stats,
+                        const float* gamma, const float* beta, int32_t act, const float* alpha, int32_t alpha_n,
+                        int32_t training, float* dx, float* dgamma, float* dbeta, float* dalpha_c, float* workspace,
+                        uint32_t* dx_max, int32_t q_out, avse_stream_t stream);
 
 /* ---------------------------------------------------------------- max pooling over planes -------
  * nn.MaxPool3d((1, KH, KW), (1, SH, SW), (0, PH, PW)) of the lip front-ends (avse1 model.py:29-34, avse4
@@ -535,6 +548,24 @@ int avse_sconv_wgrad(int64_t N, int64_t Hi, int64_t Wi, int64_t ci, int64_t co, 
                      avse_stream_t stream);
 int avse_dconv_fwd(int64_t N, int64_t H, int64_t W, int64_t dil, const void* xq, const void* wq,
                    const uint32_t* maxbits, const float* bias, float* y, avse_stream_t stream);
+/* The input gradient dx of conv_{i+1}(ReLU(BN_i(bn_x))) (model.py:199-215) = avse_dconv_fwd on the split dY and the
+ * transposed weight image, bit for bit, whose workgroups also write the BatchNorm backward's per-channel partial sums
+ * over their pixel tile (dz = dx masked by the forward's z > 0, recomputed from bn_x and bn_stats): one row of
+ * [nq][64] floats per workgroup, avse_dconv_bn_rows(N, H, W, dil) rows, nq = 4 with want_max (max |dz| too), else 3;
+ * avse_bnact_bwd_rows finishes the backward from them.  act: 1 (ReLU) only.  No atomics: deterministic. */
+int64_t avse_dconv_bn_rows(int64_t N, int64_t H, int64_t W, int64_t dil);
+int avse_dconv_dgrad_bn(int64_t N, int64_t H, int64_t W, int64_t dil, const void* dyq, const void* wq_t,
+                        const uint32_t* maxbits, float* dx, const float* bn_x, const float* bn_stats,
+                        const float* gamma, const float* beta, int32_t act, int32_t want_max, float* rows,
+                        avse_stream_t stream);
+/* The same for the stride-1 trunk convolution conv2(PReLU(bn1(bn_x))) of a BasicBlock (resnet.py:40-67): dx (N, H, W,
+ * co) = avse_sconv_fwd(N, H, W, ci, co, 1, dyq, ...) on the transposed = 1 weight image, bit for bit, plus one row of
+ * [nq][co] floats per pixel tile (avse_sconv_bn_rows rows).  act: 2 (PReLU) only, alpha_n 1 or co. */
+int64_t avse_sconv_bn_rows(int64_t N, int64_t H, int64_t W, int64_t co);
+int avse_sconv_dgrad1_bn(int64_t N, int64_t H, int64_t W, int64_t ci, int64_t co, const void* dyq,
+                         const uint32_t* dymax, const void* wq_t, const uint32_t* wmax, float* dx, const float* bn_x,
+                         const float* bn_stats, const float* gamma, const float* beta, int32_t act, const float* alpha,
+                         int32_t alpha_n, int32_t want_max, float* rows, avse_stream_t stream);
 /* Weight (and bias) gradient of the same convolution from the split input xq (max bits *xmax) and the split output
  * gradient dyq (*dymax): dw (64, 64, 5, 5), db (64) or NULL; workspace avse_dconv_wgrad16_workspace_bytes(). */
 int64_t avse_dconv_wgrad16_workspace_bytes(int64_t N, int64_t H, int64_t W);

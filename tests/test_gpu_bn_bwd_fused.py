@@ -1,0 +1,200 @@
+"""BatchNorm-backward sums taken from the epilogue of the split-fp16 input-gradient convolutions (csrc/bnact_cols.h,
+avse_dconv_dgrad_bn / avse_sconv_dgrad1_bn / avse_bnact_bwd_rows) against the unfused kernels and torch fp64.
+
+Shapes: the smallest that reach every tile case.  Dilated (2, 64, 6, 257): W = 257 is the kernel's minimum class, the
+1542 pixels per image give tiles that span 2 and 3 rows and a ragged last tile for both tile sizes (256 pixels at
+d = 2, 512 at d = 16).  Trunk (5, 64, 6, 6): TN = 64, one ragged 512-pixel tile; (9, 128, 7, 5): TN = 128, two
+256-pixel tiles, the second ragged.
+
+Bars: dx / dgamma / dbeta / dalpha against fp64 are those of test_bnact_vs_fp64; against the unfused bnact_bwd on the
+same dy the mask is identical and only the two per-channel means k1, k2 move by the rounding of a re-ordered fp32 sum,
+so dx agrees to 1e-6 max |dx|; the split output's bars are those of test_bnact_split_output_vs_fp32."""
+import pytest
+import torch
+
+from oracle.det_init import det_input
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+
+
+def K():
+    from avse_challenge_amd import kernels
+    return kernels
+
+
+def _q_decode(t):
+    """A split-output (N, C, H, W) tensor -> fp64 values (hi + lo) 2^-e, e from its bound (dconv.hip split_exp)."""
+    q = K().q_view(t).view(torch.float16).reshape(-1, t.shape[1] // 16, 2, 16).double()
+    bits = int(getattr(t, K().ABSMAX_ATTR).item())
+    e = max(-100, min(100, 14 - (((bits >> 23) & 0xFF) - 127))) if bits else 0
+    v = (q[:, :, 0, :] + q[:, :, 1, :]) * 2.0 ** -e
+    n, c, h, w = t.shape
+    return v.reshape(n, h, w, c).permute(0, 3, 1, 2)
+
+
+def _cl(t):
+    return t.float().to(DEV).contiguous(memory_format=torch.channels_last)
+
+
+def _bn_inputs(shape, mean, scale, act):
+    C = shape[1]
+    g = torch.Generator().manual_seed(C + shape[-1])
+    x = _cl(scale * det_input(shape, 760) + mean)
+    gam = (0.5 + torch.rand(C, generator=g)).to(DEV)
+    bet = (0.1 * torch.randn(C, generator=g)).to(DEV)
+    alpha = (0.1 + 0.3 * torch.rand(C, generator=g)).to(DEV) if act == "prelu_c" else None
+    code = K().ACT_PRELU if act == "prelu_c" else K().ACT_RELU
+    _, stats = K().bnact_fwd(x, gam, bet, torch.zeros(C, device=DEV), torch.ones(C, device=DEV), True, 0.1, 1e-5, code,
+                             alpha, q_out=True)
+    return x, gam, bet, alpha, code, stats
+
+
+def _fp64_bwd(x, gam, bet, alpha, dy):
+    """torch fp64 BatchNorm (batch statistics, eps 1e-5) -> ReLU / PReLU backward with dy as the upstream gradient."""
+    xd = x.double().cpu().requires_grad_(True)
+    gd, bd = gam.double().cpu().requires_grad_(True), bet.double().cpu().requires_grad_(True)
+    z = torch.nn.functional.batch_norm(xd, None, None, gd, bd, True, 0.1, 1e-5)
+    if alpha is None:
+        ad, y = None, torch.relu(z)
+    else:
+        ad = alpha.double().cpu().requires_grad_(True)
+        y = torch.nn.functional.prelu(z, ad)
+    y.backward(dy.double().cpu())
+    return xd.grad, gd.grad, bd.grad, None if ad is None else ad.grad
+
+
+def _close(a, b, atol, rtol, what):
+    a, b = a.detach().double().cpu(), b.detach().double().cpu()
+    err = (a - b).abs()
+    lim = atol + rtol * b.abs()
+    print(f"{what}: max err {float(err.max()):.3e} (atol {atol:.3e})")
+    assert bool((err <= lim).all()), (what, float(err.max()), atol)
+
+
+def _nan_ws(monkeypatch):
+    """The rows workspace NaN-filled before the producer writes it: a slice no workgroup wrote shows in every sum."""
+    real = K()._bn_rows_ws
+    monkeypatch.setattr(K(), "_bn_rows_ws", lambda *a: real(*a).fill_(float("nan")))
+
+
+def _check(x, gam, bet, alpha, code, stats, dy_ref, fused, q_out):
+    """fused(q) -> (dy, rows, ws) of the epilogue launch with want_max = q.  The fp32 result of bnact_bwd_rows takes
+    checks 1-3, 5, 6; with q_out the split result is then held against that fp32 result (the same sums: check 4)."""
+    k = K()
+
+    def run(q):
+        dy, rows, ws = fused(q)
+        return (dy,) + k.bnact_bwd_rows(x, dy, stats, gam, bet, code, alpha, True, rows, ws, q_out=q)
+
+    outs = [run(q_out), run(q_out)]
+    for a, b in zip(outs[0], outs[1]):                               # 6: deterministic
+        if a is not None:
+            assert torch.equal(a.view(torch.int32), b.view(torch.int32))
+    assert torch.equal(outs[0][0], dy_ref)                           # 1: the conv output is untouched
+    dy, dx, _, dg, db, da = outs[0] if not q_out else run(False)
+    assert torch.equal(dy, dy_ref) and not k.is_split_q(dx)
+    assert int(getattr(dx, k.ABSMAX_ATTR).item()) == int(dx.abs().max().view(torch.int32).item())
+    rdx, rdg, rdb, rda = _fp64_bwd(x, gam, bet, alpha, dy)          # 2: fp64, fed the GPU dy
+    _close(dx, rdx, 2e-5 * float(rdx.abs().max()), 1e-4, "dx vs fp64")
+    _close(dg, rdg, 1e-4 * float(rdg.abs().max()), 1e-4, "dgamma")
+    _close(db, rdb, 1e-4 * float(rdb.abs().max()), 1e-4, "dbeta")
+    if alpha is not None:
+        _close(da, rda, 1e-4 * float(rda.abs().max()), 1e-4, "dalpha")
+    ux = k.bnact_bwd(x, None, dy, stats, gam, bet, code, alpha, True)[0]    # 3: the unfused fp32 path
+    _close(dx, ux, 1e-6 * float(ux.abs().max()), 0.0, "dx vs unfused")
+    if q_out:                                                        # 4: the split planes and their bound
+        _, dxq, _, dgq, dbq, daq = outs[0]
+        assert k.is_split_q(dxq) and torch.equal(dg, dgq) and torch.equal(db, dbq)
+        assert alpha is None or torch.equal(da, daq)
+        m = float(dx.abs().max())
+        bound = float(getattr(dxq, k.ABSMAX_ATTR).view(torch.float32).item())
+        print(f"max |dx| {m:.3e} bound {bound:.3e}")
+        assert m <= bound <= 64 * m, (m, bound)
+        _close(_q_decode(dxq), dx, 2.0 ** -21 * m, 0.0, "decoded dx")
+
+
+@pytest.mark.parametrize("q_out", [False, True])
+@pytest.mark.parametrize("mean,scale", [(0.0, 1.0), (30.0, 0.02)])
+@pytest.mark.parametrize("d", [2, 16])
+def test_dilated_dgrad_bn_rows(d, mean, scale, q_out, monkeypatch):
+    """conv_{i+1}(ReLU(BN_i(x))): the dilated input gradient with the epilogue, then bnact_bwd_rows."""
+    k = K()
+    shape = (2, 64, 6, 257)
+    x, gam, bet, alpha, code, stats = _bn_inputs(shape, mean, scale, "relu")
+    w = (0.05 * det_input((64, 64, 5, 5), 761)).float().to(DEV)
+    g = _cl(det_input(shape, 762))                                   # gradient of the conv's output
+    mb, mbd = (torch.empty(2, device=DEV, dtype=torch.int32) for _ in range(2))
+    gq = k.split16(g, mbd)
+    _, wq_t = k.dconv_wprep2(w, mb, mbd)
+    dy_ref = k.dconv_fwd(g, w, d, transposed=True, split=(gq, mbd), wq=wq_t)
+    _nan_ws(monkeypatch)
+    _check(x, gam, bet, alpha, code, stats, dy_ref,
+           lambda q: k.dconv_dgrad_bn(shape, d, (gq, mbd), wq_t, x, stats, gam, bet, code, q), q_out)
+
+
+@pytest.mark.parametrize("q_out", [False, True])
+@pytest.mark.parametrize("mean,scale", [(0.0, 1.0), (30.0, 0.02)])
+@pytest.mark.parametrize("shape", [(5, 64, 6, 6), (9, 128, 7, 5)])
+def test_trunk_dgrad_bn_rows(shape, mean, scale, q_out, monkeypatch):
+    """conv2(PReLU(bn1(x))) of a BasicBlock: the stride-1 trunk input gradient with the epilogue, then bnact_bwd_rows."""
+    k = K()
+    C = shape[1]
+    x, gam, bet, alpha, code, stats = _bn_inputs(shape, mean, scale, "prelu_c")
+    w = (0.05 * det_input((C, C, 3, 3), 763)).float().to(DEV)
+    g = _cl(det_input(shape, 764))
+    gs = k.split_q(g)
+    dy_ref = k.sconv_fwd(gs, shape, w, 1, transposed=True)
+    _nan_ws(monkeypatch)
+    _check(x, gam, bet, alpha, code, stats, dy_ref,
+           lambda q: k.sconv_dgrad1_bn(gs, shape, w, x, stats, gam, bet, code, alpha, q), q_out)
+
+
+@pytest.mark.parametrize("kind", ["dilated", "trunk"])
+def test_paired_autograd_uses_rows(kind, monkeypatch):
+    """bn_act(q_fwd) -> split conv through autograd: the BatchNorm's backward takes the conv's rows (one
+    bnact_bwd_rows call, no unfused bnact_bwd for that BatchNorm), and every gradient agrees with the unpaired graph:
+    the conv's own gradients bit for bit, the BatchNorm's within the re-ordered sums' rounding."""
+    from avse_challenge_amd import layers
+    k = K()
+    torch.manual_seed(3)
+    if kind == "dilated":
+        shape, act = (2, 64, 6, 257), "relu"
+        conv = layers.DilatedConv2d(64, 64, 5, padding=4, dilation=2).to(DEV)
+    else:
+        shape = (5, 64, 6, 6)
+        act = layers.PReLU(64).to(DEV)
+        conv = layers.TrunkConv2d(64, 64).to(DEV)
+    bn = torch.nn.BatchNorm2d(64).to(DEV).train()
+    with torch.no_grad():
+        bn.weight.uniform_(0.5, 1.5)
+        bn.bias.normal_(0.0, 0.1)
+    x0 = _cl(det_input(shape, 765))
+    gy = _cl(det_input(shape, 766))
+    params = [bn.weight, bn.bias, conv.weight] + ([act.weight] if kind == "trunk" else [])
+
+    def run():
+        for p in params:
+            p.grad = None
+        x = x0.clone(memory_format=torch.preserve_format).requires_grad_(True)
+        h = layers.bn_act(x, bn, act, q_fwd=conv.q_ok(x))
+        assert k.is_split_q(h)
+        conv(h).backward(gy)
+        return [x.grad.clone()] + [p.grad.clone() for p in params]
+
+    calls = {"rows": 0, "plain": 0}
+    real_rows, real_plain = k.bnact_bwd_rows, k.bnact_bwd
+    monkeypatch.setattr(k, "bnact_bwd_rows", lambda *a, **kw: (calls.__setitem__("rows", calls["rows"] + 1),
+                                                               real_rows(*a, **kw))[1])
+    monkeypatch.setattr(k, "bnact_bwd", lambda *a, **kw: (calls.__setitem__("plain", calls["plain"] + 1),
+                                                          real_plain(*a, **kw))[1])
+    fused = run()
+    assert calls == {"rows": 1, "plain": 0}, calls
+    monkeypatch.setattr(layers._BNPair, "of", staticmethod(lambda t, a: None))
+    plain = run()
+    assert calls == {"rows": 1, "plain": 1}, calls
+    assert torch.equal(fused[3], plain[3])                           # the conv's weight gradient
+    m = float(plain[0].abs().max())
+    _close(fused[0], plain[0], 1e-6 * m, 0.0, "dx")
+    for a, b, what in zip(fused[1:3] + fused[4:], plain[1:3] + plain[4:], ("dgamma", "dbeta", "dalpha")):
+        _close(a, b, 1e-5 * float(b.abs().max()), 0.0, what)
