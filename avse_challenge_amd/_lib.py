@@ -66,6 +66,32 @@ class ScanBwdArgs(ctypes.Structure):
     ]
 
 
+class ScanFwdStateArgs(ctypes.Structure):
+    """avse_scan_fwd_state_args: the forward scan's fields (s) and the carried state."""
+    _fields_ = [
+        ("s", ScanFwdArgs),
+        ("h0", c_vp), ("h0_bs", c_i64), ("h0_ds", c_i64),
+        ("h_last", c_vp), ("h_last_bs", c_i64), ("h_last_ds", c_i64),
+    ]
+
+
+class SsmStepArgs(ctypes.Structure):
+    _fields_ = [
+        ("batch", c_i64), ("dim", c_i64), ("dstate", c_i64),
+        ("dtype", c_i32), ("dt_softplus", c_i32),
+        ("state", c_vp), ("state_bs", c_i64), ("state_ds", c_i64),
+        ("x", c_vp), ("x_bs", c_i64),
+        ("dt", c_vp), ("dt_bs", c_i64),
+        ("A", c_vp),
+        ("B", c_vp), ("B_bs", c_i64),
+        ("C", c_vp), ("C_bs", c_i64),
+        ("D", c_vp),
+        ("z", c_vp), ("z_bs", c_i64),
+        ("dt_bias", c_vp),
+        ("out", c_vp), ("out_bs", c_i64),
+    ]
+
+
 class GemmBf16Args(ctypes.Structure):
     _fields_ = [
         ("batch", c_i64), ("mp", c_i64), ("mq", c_i64), ("k", c_i64), ("fold", c_i64),
@@ -97,6 +123,8 @@ SIGNATURES = {
     "avse_scan_bwd_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_i64]),
     "avse_scan_fwd": (c_i32, [ctypes.POINTER(ScanFwdArgs), c_vp]),
     "avse_scan_bwd": (c_i32, [ctypes.POINTER(ScanBwdArgs), c_vp]),
+    "avse_scan_fwd_state": (c_i32, [ctypes.POINTER(ScanFwdStateArgs), c_vp]),
+    "avse_ssm_step": (c_i32, [ctypes.POINTER(SsmStepArgs), c_vp]),
     "avse_dtproj": (c_i32, [c_i64, c_i64, c_i64, c_i64, c_i32, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i32, c_vp, c_i64,
                             c_i64, c_vp]),
     "avse_cconv_bwd_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64]),
@@ -108,6 +136,12 @@ SIGNATURES = {
                                c_vp, c_i64, c_i64, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp]),
     "avse_cconv_bwd_bf16": (c_i32, [c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64,
                                     c_vp, c_i64, c_i64, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp]),
+    "avse_cconv_fwd_state": (c_i32, [c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64,
+                                     c_i32, c_vp, c_vp, c_i64, c_i64, c_vp]),
+    "avse_cconv_fwd_state_bf16": (c_i32, [c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64,
+                                          c_i64, c_i32, c_vp, c_vp, c_i64, c_i64, c_vp]),
+    "avse_cconv_update": (c_i32, [c_i64, c_i64, c_i64, c_i32, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64,
+                                  c_i32, c_vp]),
     "avse_add_rmsnorm_fwd": (c_i32, [c_i64, c_i64, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "avse_rmsnorm_bwd_workspace_bytes": (c_i64, [c_i64, c_i64]),
     "avse_rmsnorm_bwd": (c_i32, [c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),

@@ -469,6 +469,192 @@ __global__ __launch_bounds__(THREADS) void bwd_short_kernel(int rows, int D, int
     }
 }
 
+// ---------------------------------------------------------------- carried left context (streaming inference)
+// The three forward paths again, continuing a row from a cached conv_state (b, d, W) = the row's last W inputs,
+// oldest first (bimamba.py:277,328-329): x[-j] = state[W - j].  One owner thread per row (thread 0 of the row's
+// workgroup; lane 0 of its wave on the short path) reads the old state into registers before anything else, hands
+// the halo to the row's other threads (LDS) and, at the end, writes the new state = the last W of
+// concat(old state, x), reading the row's last inputs itself: no other thread touches the state, so state_out may
+// alias state_in.  Forward time order only.
+template <typename T>
+struct CState {
+    const T* in;      // NULL: zeros
+    T* out;           // NULL: not stored
+    int64_t bs, ds;
+};
+
+// the old state as four named floats (W <= 4; entries past W are 0): selects between them stay in registers
+__device__ inline float old_at(const float4& o, int k) { return k == 0 ? o.x : k == 1 ? o.y : k == 2 ? o.z : o.w; }
+
+template <typename T, int W>
+__device__ inline float4 state_load(const CState<T>& cs, int b, int d) {
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
+    if (cs.in) {
+        const T* si = cs.in + b * cs.bs + (int64_t)d * cs.ds;
+#pragma unroll
+        for (int k = 0; k < W; ++k) v[k] = io<T>::ld(&si[k]);
+    }
+    return make_float4(v[0], v[1], v[2], v[3]);
+}
+
+template <typename T, int W>
+__device__ inline void state_store(const CState<T>& cs, int b, int d, const float4& old, const T* xr, int L) {
+    if (!cs.out) return;
+    T* so = cs.out + b * cs.bs + (int64_t)d * cs.ds;
+#pragma unroll
+    for (int j = 0; j < W; ++j) {
+        const int c = L + j;                       // index into concat(old, x); c >= 1
+        if (c >= W) {
+            so[j] = xr[c - W];                     // raw copy: the state holds the inputs bit for bit
+        } else {                                   // l < w: an old entry moves left (fp32 <-> T round trip is exact)
+            float v = old_at(old, W - 1);
+            if (W > 2 && c == 1) v = old.y;
+            if (W > 3 && c == 2) v = old.z;
+            io<T>::st(&so[j], v);
+        }
+    }
+}
+
+template <typename T, int W, bool SILU, bool HAS_BIAS>
+__global__ __launch_bounds__(THREADS) void fwd_state_kernel(int D, int L, const T* __restrict__ x, int64_t x_bs,
+                                                            int64_t x_ds, const float* __restrict__ w,
+                                                            const float* __restrict__ bias, T* __restrict__ out,
+                                                            int64_t o_bs, int64_t o_ds, CState<T> cs) {
+    __shared__ float s[TILE + MAXW];
+    const int row = blockIdx.x;
+    const int b = row / D, d = row % D;
+    const T* xr = x + b * x_bs + (int64_t)d * x_ds;
+    T* orow = out + b * o_bs + (int64_t)d * o_ds;
+    float4 old = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (threadIdx.x == 0) old = state_load<T, W>(cs, b, d);
+    float wk[W];
+#pragma unroll
+    for (int k = 0; k < W; ++k) wk[k] = w[d * W + k];
+    const float bv = HAS_BIAS ? bias[d] : 0.f;
+    for (int t0 = 0; t0 < L; t0 += TILE) {
+        __syncthreads();
+        // s[i] holds x[t0 - (W-1) + i]; the t < 0 entries of the first tile come from the old state
+        for (int i = threadIdx.x; i < TILE + W - 1; i += THREADS) {
+            const int t = t0 - (W - 1) + i;
+            if (t >= 0) s[i] = t < L ? io<T>::ld(&xr[t]) : 0.f;
+        }
+        if (t0 == 0 && threadIdx.x == 0) {
+#pragma unroll
+            for (int k = 0; k < W - 1; ++k) s[k] = old_at(old, k + 1);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int p = 0; p < PER; ++p) {
+            const int i = threadIdx.x + p * THREADS, t = t0 + i;
+            if (t < L) {
+                float acc = bv;
+#pragma unroll
+                for (int k = 0; k < W; ++k) acc += wk[k] * s[i + k];
+                io<T>::st(&orow[t], SILU ? siluf_(acc) : acc);
+            }
+        }
+    }
+    if (threadIdx.x == 0) state_store<T, W>(cs, b, d, old, xr, L);
+}
+
+template <typename T, int W, bool SILU, bool HAS_BIAS>
+__global__ __launch_bounds__(THREADS) void fwd_vec_state_kernel(int D, int L, const T* __restrict__ x, int64_t x_bs,
+                                                                int64_t x_ds, const float* __restrict__ w,
+                                                                const float* __restrict__ bias, T* __restrict__ out,
+                                                                int64_t o_bs, int64_t o_ds, CState<T> cs) {
+    const int row = blockIdx.x;
+    const int b = row / D, d = row % D;
+    const T* xr = x + b * x_bs + (int64_t)d * x_ds;
+    T* orow = out + b * o_bs + (int64_t)d * o_ds;
+    float4 old = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (threadIdx.x == 0) old = state_load<T, W>(cs, b, d);
+    float wk[W];
+#pragma unroll
+    for (int k = 0; k < W; ++k) wk[k] = w[d * W + k];
+    const float bv = HAS_BIAS ? bias[d] : 0.f;
+    for (int t = threadIdx.x * 4; t < L; t += THREADS * 4) {
+        float e[8], o[4];                         // e[i] = x[t - 4 + i]
+        ld4z<T>(xr, t - 4, L, e);
+        if (t == 0) {                             // thread 0 only: the halo is the old state
+#pragma unroll
+            for (int k = 0; k < W - 1; ++k) e[4 - (W - 1) + k] = old_at(old, k + 1);
+        }
+        ld4z<T>(xr, t, L, e + 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float acc = bv;
+#pragma unroll
+            for (int k = 0; k < W; ++k) acc = fmaf(wk[k], e[4 + j - (W - 1) + k], acc);
+            o[j] = SILU ? siluf_(acc) : acc;
+        }
+        st4<T>(orow, t, L, o);
+    }
+    if (threadIdx.x == 0) state_store<T, W>(cs, b, d, old, xr, L);
+}
+
+template <typename T, int W, bool SILU, bool HAS_BIAS>
+__global__ __launch_bounds__(THREADS) void fwd_short_state_kernel(int rows, int D, int L, const T* __restrict__ x,
+                                                                  int64_t x_bs, int64_t x_ds,
+                                                                  const float* __restrict__ w,
+                                                                  const float* __restrict__ bias, T* __restrict__ out,
+                                                                  int64_t o_bs, int64_t o_ds, CState<T> cs) {
+    __shared__ float s[4][SPAD];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + wave;
+    if (row >= rows) return;                       // no workgroup barrier below: rows are wave-private
+    const int b = row / D, d = row % D;
+    const T* xr = x + b * x_bs + (int64_t)d * x_ds;
+    T* orow = out + b * o_bs + (int64_t)d * o_ds;
+    float* sw = s[wave];
+    float4 old = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (lane == 0) {
+        old = state_load<T, W>(cs, b, d);
+#pragma unroll
+        for (int k = 0; k < W - 1; ++k) sw[k] = old_at(old, k + 1);
+    }
+    for (int i = lane; i < L + W - 1; i += 64) {   // sw[i] = x[i - (W-1)]
+        const int t = i - (W - 1);
+        if (t >= 0) sw[i] = io<T>::ld(&xr[t]);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    float wk[W];
+#pragma unroll
+    for (int k = 0; k < W; ++k) wk[k] = w[d * W + k];
+    const float bv = HAS_BIAS ? bias[d] : 0.f;
+    for (int t = lane; t < L; t += 64) {
+        float acc = bv;
+#pragma unroll
+        for (int k = 0; k < W; ++k) acc += wk[k] * sw[t + k];
+        io<T>::st(&orow[t], SILU ? siluf_(acc) : acc);
+    }
+    if (lane == 0) state_store<T, W>(cs, b, d, old, xr, L);
+}
+
+// causal_conv1d_update (bimamba.py:328-333): one thread per (b, d) row rolls its W-sample state and takes the dot
+// product; x / out are (b, d) with d contiguous, so consecutive threads read consecutive elements
+template <typename T, int W, bool SILU, bool HAS_BIAS>
+__global__ __launch_bounds__(THREADS) void update_kernel(int rows, int D, const T* __restrict__ x, int64_t x_bs,
+                                                         T* st, int64_t st_bs, int64_t st_ds,
+                                                         const float* __restrict__ w, const float* __restrict__ bias,
+                                                         T* __restrict__ out, int64_t o_bs) {
+    const int row = blockIdx.x * THREADS + threadIdx.x;
+    if (row >= rows) return;
+    const int b = row / D, d = row % D;
+    T* sp = st + b * st_bs + (int64_t)d * st_ds;
+    T v[W];
+#pragma unroll
+    for (int k = 0; k < W - 1; ++k) v[k] = sp[k + 1];
+    v[W - 1] = x[b * x_bs + d];
+    float acc = HAS_BIAS ? bias[d] : 0.f;
+#pragma unroll
+    for (int k = 0; k < W; ++k) acc += w[d * W + k] * io<T>::ld(&v[k]);
+#pragma unroll
+    for (int k = 0; k < W; ++k) sp[k] = v[k];
+    io<T>::st(&out[b * o_bs + d], SILU ? siluf_(acc) : acc);
+}
+
 // dweight / dbias: per-row partials summed over the batch, one workgroup per channel (deterministic:
 // fixed per-thread strides, then a fixed tree)
 // max over the rows' wsmax entries -> *out (atomic max: the scan's dz max may share the word)
@@ -572,6 +758,29 @@ void launch_bwd(int64_t batch, int64_t dim, int64_t seqlen, const T* x, int64_t 
                            dx_max);
 }
 
+template <typename T, int W, bool S, bool HB>
+void launch_fwd_state(int64_t batch, int64_t dim, int64_t seqlen, const T* x, int64_t x_bs, int64_t x_ds, const float* w,
+                      const float* bias, T* out, int64_t o_bs, int64_t o_ds, CState<T> cs, hipStream_t st) {
+    const int rows = (int)(batch * dim);
+    if (seqlen <= SHORT_L)
+        hipLaunchKernelGGL((fwd_short_state_kernel<T, W, S, HB>), dim3((unsigned)((rows + 3) / 4)), dim3(THREADS), 0, st,
+                           rows, (int)dim, (int)seqlen, x, x_bs, x_ds, w, bias, out, o_bs, o_ds, cs);
+    else if (vec_rows<T>(x, x_bs, x_ds, seqlen, true) && vec_rows<T>(out, o_bs, o_ds, seqlen, false))
+        hipLaunchKernelGGL((fwd_vec_state_kernel<T, W, S, HB>), dim3((unsigned)rows), dim3(THREADS), 0, st, (int)dim,
+                           (int)seqlen, x, x_bs, x_ds, w, bias, out, o_bs, o_ds, cs);
+    else
+        hipLaunchKernelGGL((fwd_state_kernel<T, W, S, HB>), dim3((unsigned)rows), dim3(THREADS), 0, st, (int)dim,
+                           (int)seqlen, x, x_bs, x_ds, w, bias, out, o_bs, o_ds, cs);
+}
+
+template <typename T, int W, bool S, bool HB>
+void launch_update(int64_t batch, int64_t dim, const T* x, int64_t x_bs, T* state, int64_t st_bs, int64_t st_ds,
+                   const float* w, const float* bias, T* out, int64_t o_bs, hipStream_t st) {
+    const int rows = (int)(batch * dim);
+    hipLaunchKernelGGL((update_kernel<T, W, S, HB>), dim3((unsigned)((rows + THREADS - 1) / THREADS)), dim3(THREADS), 0,
+                       st, rows, (int)dim, x, x_bs, state, st_bs, st_ds, w, bias, out, o_bs);
+}
+
 // width / silu / bias -> template instance
 template <template <typename, int, bool, bool> class F, typename T, typename... Args>
 int dispatch(int64_t width, bool silu, bool has_bias, Args... args) {
@@ -600,6 +809,41 @@ template <typename T, int W, bool S, bool HB>
 struct Bwd {
     template <typename... A> static void run(A... a) { launch_bwd<T, W, S, HB>(a...); }
 };
+
+template <typename T, int W, bool S, bool HB>
+struct FwdState {
+    template <typename... A> static void run(A... a) { launch_fwd_state<T, W, S, HB>(a...); }
+};
+template <typename T, int W, bool S, bool HB>
+struct Update {
+    template <typename... A> static void run(A... a) { launch_update<T, W, S, HB>(a...); }
+};
+
+template <typename T>
+int cconv_fwd_state(int64_t batch, int64_t dim, int64_t seqlen, int64_t width, const T* x, int64_t x_bs, int64_t x_ds,
+                    const float* weight, const float* bias, T* out, int64_t out_bs, int64_t out_ds, int32_t silu,
+                    const T* state_in, T* state_out, int64_t st_bs, int64_t st_ds, avse_stream_t stream) {
+    if (!x || !weight || !out) return AVSE_EINVAL;
+    if (batch <= 0 || dim <= 0 || seqlen <= 0 || width < 1 || width > MAXW) return AVSE_ESHAPE;
+    if (batch * dim > (1LL << 31) - 1) return AVSE_ESHAPE;
+    const CState<T> cs{state_in, state_out, st_bs, st_ds};
+    const int rc = dispatch<FwdState, T>(width, silu != 0, bias != nullptr, batch, dim, seqlen, x, x_bs, x_ds, weight,
+                                         bias, out, out_bs, out_ds, cs, (hipStream_t)stream);
+    if (rc != AVSE_OK) return rc;
+    AVSE_CHECK_LAUNCH();
+    return AVSE_OK;
+}
+
+template <typename T>
+int cconv_update(int64_t batch, int64_t dim, int64_t width, const T* x, int64_t x_bs, T* state, int64_t st_bs,
+                 int64_t st_ds, const float* weight, const float* bias, T* out, int64_t out_bs, int32_t silu,
+                 avse_stream_t stream) {
+    const int rc = dispatch<Update, T>(width, silu != 0, bias != nullptr, batch, dim, x, x_bs, state, st_bs, st_ds,
+                                       weight, bias, out, out_bs, (hipStream_t)stream);
+    if (rc != AVSE_OK) return rc;
+    AVSE_CHECK_LAUNCH();
+    return AVSE_OK;
+}
 
 template <typename T>
 int cconv_fwd(int64_t batch, int64_t dim, int64_t seqlen, int64_t width, const T* x, int64_t x_bs, int64_t x_ds,
@@ -656,6 +900,38 @@ int avse_cconv_fwd(int64_t batch, int64_t dim, int64_t seqlen, int64_t width, co
                    int32_t silu, int32_t reverse, avse_stream_t stream) {
     return cconv_fwd<float>(batch, dim, seqlen, width, x, x_bs, x_ds, weight, bias, out, out_bs, out_ds, silu,
                             reverse, stream);
+}
+
+int avse_cconv_fwd_state(int64_t batch, int64_t dim, int64_t seqlen, int64_t width, const float* x, int64_t x_bs,
+                         int64_t x_ds, const float* weight, const float* bias, float* out, int64_t out_bs,
+                         int64_t out_ds, int32_t silu, const float* state_in, float* state_out, int64_t st_bs,
+                         int64_t st_ds, avse_stream_t stream) {
+    return cconv_fwd_state<float>(batch, dim, seqlen, width, x, x_bs, x_ds, weight, bias, out, out_bs, out_ds, silu,
+                                  state_in, state_out, st_bs, st_ds, stream);
+}
+
+int avse_cconv_fwd_state_bf16(int64_t batch, int64_t dim, int64_t seqlen, int64_t width, const uint16_t* x,
+                              int64_t x_bs, int64_t x_ds, const float* weight, const float* bias, uint16_t* out,
+                              int64_t out_bs, int64_t out_ds, int32_t silu, const uint16_t* state_in,
+                              uint16_t* state_out, int64_t st_bs, int64_t st_ds, avse_stream_t stream) {
+    return cconv_fwd_state<bf16_t>(batch, dim, seqlen, width, (const bf16_t*)x, x_bs, x_ds, weight, bias, (bf16_t*)out,
+                                   out_bs, out_ds, silu, (const bf16_t*)state_in, (bf16_t*)state_out, st_bs, st_ds,
+                                   stream);
+}
+
+int avse_cconv_update(int64_t batch, int64_t dim, int64_t width, int32_t dtype, const void* x, int64_t x_bs,
+                      void* conv_state, int64_t st_bs, int64_t st_ds, const float* weight, const float* bias, void* out,
+                      int64_t out_bs, int32_t silu, avse_stream_t stream) {
+    if (!x || !conv_state || !weight || !out) return AVSE_EINVAL;
+    if (batch <= 0 || dim <= 0 || width < 1 || width > MAXW) return AVSE_ESHAPE;
+    if (batch * dim > (1LL << 31) - 1) return AVSE_ESHAPE;
+    if (dtype == AVSE_F32)
+        return cconv_update<float>(batch, dim, width, (const float*)x, x_bs, (float*)conv_state, st_bs, st_ds, weight,
+                                   bias, (float*)out, out_bs, silu, stream);
+    if (dtype == AVSE_BF16)
+        return cconv_update<bf16_t>(batch, dim, width, (const bf16_t*)x, x_bs, (bf16_t*)conv_state, st_bs, st_ds,
+                                    weight, bias, (bf16_t*)out, out_bs, silu, stream);
+    return AVSE_EDTYPE;
 }
 
 int avse_cconv_bwd(int64_t batch, int64_t dim, int64_t seqlen, int64_t width, const float* x, int64_t x_bs,

@@ -359,6 +359,168 @@ __global__ __launch_bounds__(THREADS) void fwd_kernel(avse_scan_fwd_args a, int 
     if (HAS_Z && a.out_z_max) block_absmax_to(zmax, a.out_z_max);     // a.out_z_max: uniform over the grid
 }
 
+// ------------------------------------------------------------------------------- forward with carried state
+// avse_scan_fwd_state (streaming inference): fwd_kernel's sibling, kept apart so that the training kernels' code does
+// not move.  Same staging, recurrence and flush; differences: the lane that holds states 4g .. 4g+3 of channel d seeds
+// them from h0 and stores them to h_last after the last step (so h_last may alias h0), the checkpoints x are optional,
+// time runs forwards only and there is neither out_z accumulation nor its max.
+struct CarriedState {
+    const float* h0;   int64_t h0_bs, h0_ds;      // (b, d, 16) fp32 or NULL (zeros)
+    float* h_last;     int64_t hl_bs, hl_ds;      // (b, d, 16) fp32 or NULL (not stored)
+};
+
+template <typename Tin, bool HAS_Z, bool HAS_D, bool HAS_BIAS, bool SOFTPLUS>
+__global__ __launch_bounds__(THREADS) void fwd_state_kernel(avse_scan_fwd_args a, int nblk_d, CarriedState hs) {
+    __shared__ __attribute__((aligned(16))) float s_ud[CPB * UD_STRIDE];
+    __shared__ __attribute__((aligned(16))) float s_bc[TC * BC_STRIDE];
+    __shared__ float2 s_par[CPB];                      // (delta_bias, D) per row of the block
+
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);
+    const int b = bid / nblk_d, d0 = (bid % nblk_d) * CPB;
+    const int D = (int)a.dim, L = (int)a.seqlen;
+    constexpr bool rev = false;                        // causal inference only (validated on the host)
+    const Lane id = lane_ids();
+    const int d = d0 + id.c;
+    const bool dvalid = d < D;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (threadIdx.x < CPB) {
+        const int r = d0 + (int)threadIdx.x;
+        s_par[threadIdx.x] = make_float2((HAS_BIAS && r < D) ? a.delta_bias[r] : 0.f, (HAS_D && r < D) ? a.D[r] : 0.f);
+    }
+
+    // the lane's 4 states as 2 packed pairs: every state update is v_pk_mul / v_pk_fma on pairs
+    f2_t A2v[NS / 2], h2[NS / 2];
+#pragma unroll
+    for (int p = 0; p < NS / 2; ++p) {
+        const int j = id.g * NS + 2 * p;
+        A2v[p] = dvalid ? f2_t{a.A[(int64_t)d * NSTATE + j], a.A[(int64_t)d * NSTATE + j + 1]} * AVSE_LOG2E : f2_t{0.f, 0.f};
+        h2[p] = f2_t{0.f, 0.f};
+    }
+    if (hs.h0 && dvalid) {
+        const float4 v = *reinterpret_cast<const float4*>(hs.h0 + b * hs.h0_bs + (int64_t)d * hs.h0_ds + id.g * NS);
+        h2[0] = f2_t{v.x, v.y};
+        h2[1] = f2_t{v.z, v.w};
+    }
+
+    const Tin* u = (const Tin*)a.u;
+    const Tin* dl = (const Tin*)a.delta;
+    const Tin* z = (const Tin*)a.z;
+    const int nck = (L + TC - 1) / TC;
+    const int nck32 = (L + 31) / 32;
+    float* xrow = a.x + ((int64_t)b * D + (dvalid ? d : 0)) * nck32 * (2 * NSTATE) + 2 * id.g * NS;
+
+    const int nrow = min(CPB, D - d0);
+    RowRegs<Tin> ru, rd;
+    BCRegs<Tin> rbc;
+    ru.load(u, a.u_bs, a.u_ds, b, d0, D, 0, min(TC, L), L, rev);
+    rd.load(dl, a.delta_bs, a.delta_ds, b, d0, D, 0, min(TC, L), L, rev);
+    rbc.load((const Tin*)a.B, a.B_bs, a.B_ns, (const Tin*)a.C, a.C_bs, a.C_ns, b, 0, min(TC, L), L, rev);
+    __syncthreads();                                   // s_par
+    float du_keep[RPT];                                // D u of the thread's staged elements, added at the flush
+
+    for (int k = 0; k < nck; ++k) {
+        const int t0 = k * TC, tn = min(TC, L - t0);
+        // registers -> LDS (chunk k)
+        if (tn == TC && nrow == CPB)
+            store_fwd<Tin, SOFTPLUS, HAS_BIAS, HAS_D, true>(s_ud, ru, rd, s_par, du_keep, tn, nrow);
+        else
+            store_fwd<Tin, SOFTPLUS, HAS_BIAS, HAS_D, false>(s_ud, ru, rd, s_par, du_keep, tn, nrow);
+        rbc.store(s_bc, tn);
+        __syncthreads();
+        // prefetch chunk k + 1 while chunk k computes
+        if (k + 1 < nck) {
+            const int t1 = t0 + TC, tn1 = min(TC, L - t1);
+            ru.load(u, a.u_bs, a.u_ds, b, d0, D, t1, tn1, L, rev);
+            rd.load(dl, a.delta_bs, a.delta_ds, b, d0, D, t1, tn1, L, rev);
+            rbc.load((const Tin*)a.B, a.B_bs, a.B_ns, (const Tin*)a.C, a.C_bs, a.C_ns, b, t1, tn1, L, rev);
+        }
+
+        float* my_ud = &s_ud[id.c * UD_STRIDE];
+        // 8 steps per iteration: the LDS reads of all 8 issue together and the 8 cross-lane
+        // y reductions (DPP) are independent, so one wave per SIMD still keeps its pipes busy.
+        constexpr int U = 8;
+        auto steps = [&](int t, auto UNR) {
+            constexpr int NU = decltype(UNR)::value;
+            float yv[NU];
+#pragma unroll
+            for (int q = 0; q < NU; ++q) {
+                const float2 ud = *reinterpret_cast<const float2*>(&my_ud[2 * (t + q)]);   // (dt u, dt)
+                const float4 bq = *reinterpret_cast<const float4*>(&s_bc[(t + q) * BC_STRIDE + id.g * NS]);
+                const float4 cq = *reinterpret_cast<const float4*>(&s_bc[(t + q) * BC_STRIDE + NSTATE + id.g * NS]);
+                const f2_t bp[2] = {f2_t{bq.x, bq.y}, f2_t{bq.z, bq.w}};
+                const f2_t cp[2] = {f2_t{cq.x, cq.y}, f2_t{cq.z, cq.w}};
+                const f2_t dt2 = f2_t{ud.y, ud.y}, dtu2 = f2_t{ud.x, ud.x};
+                f2_t y2 = f2_t{0.f, 0.f};
+#pragma unroll
+                for (int p = 0; p < NS / 2; ++p) {
+                    h2[p] = exp2_2(dt2 * A2v[p]) * h2[p] + dtu2 * bp[p];
+                    y2 += h2[p] * cp[p];
+                }
+                yv[q] = y2.x + y2.y;
+            }
+#pragma unroll
+            for (int q = 0; q < NU; ++q) yv[q] = group_sum<G>(yv[q]);
+            // every lane of the channel's quad holds the same sum and writes it to the same LDS word:
+            // no exec-mask branch per step, so the NU reductions and stores schedule together
+#pragma unroll
+            for (int q = 0; q < NU; ++q) my_ud[2 * (t + q)] = yv[q];   // dt u slot <- y (D u added at the flush)
+        };
+        // always the full 64 steps: the staged tail of the last chunk is zero (dt = 0, u = 0, B = C = 0), which
+        // leaves h unchanged, so no step needs a bounds test; the state is checkpointed every 16 steps
+        // (x slot j = state after logical step 16 j + 15, clamped to the last step)
+#pragma unroll 1
+        for (int q32 = 0; q32 < TC / 32; ++q32) {
+            steps(q32 * 32, std::integral_constant<int, U>());
+            steps(q32 * 32 + U, std::integral_constant<int, U>());
+            const f2_t ha0 = h2[0], ha1 = h2[1];               // state after step 16 of the 32
+            steps(q32 * 32 + 2 * U, std::integral_constant<int, U>());
+            steps(q32 * 32 + 3 * U, std::integral_constant<int, U>());
+            const int r = k * (TC / 32) + q32;                  // x row: (after step 32r + 15, after 32r + 31)
+            if (a.x && dvalid && r < nck32) {                   // x == NULL: no checkpoints (no backward follows)
+                float4* xp = reinterpret_cast<float4*>(xrow + (int64_t)r * (2 * NSTATE));
+                xp[0] = make_float4(ha0.x, h2[0].x, ha0.y, h2[0].y);
+                xp[1] = make_float4(ha1.x, h2[1].x, ha1.y, h2[1].y);
+            }
+        }
+        RowRegs<Tin> rz;       // this chunk's z for the gate, issued before the barrier wait (issuing it with the
+        if (HAS_Z) rz.load(z, a.z_bs, a.z_ds, b, d0, D, t0, tn, L, rev);   // prefetch measured the same, round 3)
+        __syncthreads();
+        // flush chunk k outputs (lane = time column, rows wave + 4i): buffer stores, row step in soffset
+        {
+            const int nrow = min(CPB, D - d0);
+            const auto ro = make_rsrc((Tin*)a.out + b * a.out_bs + (int64_t)d0 * a.out_ds,
+                                      (int64_t)(nrow - 1) * a.out_ds + L);
+            const int vo = wave * (int)a.out_ds + tpos(t0 + lane, L, rev);
+            // rows past D need no test: their offsets lie beyond the resource's range, whose stores the hardware
+            // drops; steps past L do (inside the range they would land in the row padding), one exec mask for all
+            float outv[RPT];
+#pragma unroll
+            for (int i = 0; i < RPT; ++i) outv[i] = s_ud[(wave + 4 * i) * UD_STRIDE + 2 * lane] + du_keep[i];
+            if (a.out && lane < tn) {      // out is optional when z is given (training fwd: the bwd recomputes it)
+#pragma unroll
+                for (int i = 0; i < RPT; ++i) bufst<Tin>::st(ro, vo, 4 * i * (int)a.out_ds, outv[i]);
+            }
+            if (HAS_Z) {
+                const auto rz_ = make_rsrc((Tin*)a.out_z + b * a.out_z_bs + (int64_t)d0 * a.out_z_ds,
+                                           (int64_t)(nrow - 1) * a.out_z_ds + L);
+                const int vz = wave * (int)a.out_z_ds + tpos(t0 + lane, L, rev);
+#pragma unroll
+                for (int i = 0; i < RPT; ++i) outv[i] *= siluf_(rz.at(i));   // 16 independent gates (ILP)
+                if (lane < tn) {
+#pragma unroll
+                    for (int i = 0; i < RPT; ++i) bufst<Tin>::st(rz_, vz, 4 * i * (int)a.out_z_ds, outv[i]);
+                }
+            }
+        }
+        __syncthreads();
+    }
+    // the zero-staged tail of the last chunk left h untouched: h2 is the state after step L - 1
+    if (hs.h_last && dvalid)
+        *reinterpret_cast<float4*>(hs.h_last + b * hs.hl_bs + (int64_t)d * hs.hl_ds + id.g * NS) =
+            make_float4(h2[0].x, h2[0].y, h2[1].x, h2[1].y);
+}
+
+
 // ------------------------------------------------------------------------------- backward
 // Sum of 8 values over the 16 channel lanes (lane bits 2..5) of a wave without selects: a
 // permlane32_swap + add per pair halves 8 -> 4 values (bit 5), permlane16_swap + add halves 4 -> 2
@@ -807,6 +969,52 @@ static void launch_fwd(const avse_scan_fwd_args& a, int nblk_d, int nblocks, hip
 }
 
 template <typename Tin, bool HAS_Z, bool HAS_D, bool HAS_BIAS>
+static void launch_fwd_state(const avse_scan_fwd_args& a, const CarriedState& hs, int nblk_d, int nblocks,
+                             hipStream_t st) {
+    if (a.delta_softplus == 1)
+        hipLaunchKernelGGL((fwd_state_kernel<Tin, HAS_Z, HAS_D, HAS_BIAS, true>), dim3(nblocks), dim3(THREADS), 0, st, a,
+                           nblk_d, hs);
+    else
+        hipLaunchKernelGGL((fwd_state_kernel<Tin, HAS_Z, HAS_D, HAS_BIAS, false>), dim3(nblocks), dim3(THREADS), 0, st, a,
+                           nblk_d, hs);
+}
+
+// ------------------------------------------------------------------------------- single step
+// selective_state_update (bimamba.py:352-358) with the scan's lane mapping: 4 adjacent lanes per channel, 4 states
+// each (one 16-B state load and store per lane), y reduced over the quad by DPP.  Launch-bound at every real size.
+template <typename Tin, bool SOFTPLUS>
+__global__ __launch_bounds__(THREADS) void step_kernel(avse_ssm_step_args a) {
+    const int D = (int)a.dim;
+    const int b = blockIdx.y;
+    const int d = blockIdx.x * CPB + (int)(threadIdx.x >> 2), g = threadIdx.x & 3;
+    if (d >= D) return;                            // whole quads leave together: the DPP sums stay inside a quad
+    const Tin* Bp = (const Tin*)a.B + b * a.B_bs + g * NS;
+    const Tin* Cp = (const Tin*)a.C + b * a.C_bs + g * NS;
+    float* hp = a.state + b * a.state_bs + (int64_t)d * a.state_ds + g * NS;
+    const float4 h = *reinterpret_cast<const float4*>(hp);
+    const float4 Av = *reinterpret_cast<const float4*>(a.A + (int64_t)d * NSTATE + g * NS);
+    const float xv = io<Tin>::ld((const Tin*)a.x + b * a.x_bs + d);
+    float dt = io<Tin>::ld((const Tin*)a.dt + b * a.dt_bs + d);
+    if (a.dt_bias) dt += a.dt_bias[d];
+    if (SOFTPLUS) dt = softplus2(dt);
+    const float dtx = dt * xv;
+    const float hv[NS] = {h.x, h.y, h.z, h.w}, av[NS] = {Av.x, Av.y, Av.z, Av.w};
+    float hn[NS], y = 0.f;
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+        hn[j] = fmaf(fast_exp2(dt * (av[j] * AVSE_LOG2E)), hv[j], dtx * io<Tin>::ld(Bp + j));
+        y = fmaf(hn[j], io<Tin>::ld(Cp + j), y);
+    }
+    *reinterpret_cast<float4*>(hp) = make_float4(hn[0], hn[1], hn[2], hn[3]);
+    y = group_sum<G>(y);
+    if (g == 0) {
+        if (a.D) y = fmaf(a.D[d], xv, y);
+        if (a.z) y *= siluf_(io<Tin>::ld((const Tin*)a.z + b * a.z_bs + d));
+        io<Tin>::st((Tin*)a.out + b * a.out_bs + d, y);
+    }
+}
+
+template <typename Tin, bool HAS_Z, bool HAS_D, bool HAS_BIAS>
 static void launch_bwd(const avse_scan_bwd_args& a, int nblk_d, int nblocks, hipStream_t st) {
     const bool fold = !(HAS_Z && a.recompute_out_z);
     if constexpr (!HAS_BIAS) {
@@ -885,6 +1093,62 @@ int avse_scan_fwd(const avse_scan_fwd_args* a, avse_stream_t stream) {
     hipStream_t st = (hipStream_t)stream;
     if (a->in_dtype == AVSE_F32) AVSE_DISPATCH_FLAGS(launch_fwd, float, (*a), nblk_d, nblocks, st);
     else AVSE_DISPATCH_FLAGS(launch_fwd, bf16_t, (*a), nblk_d, nblocks, st);
+    AVSE_CHECK_LAUNCH();
+    return AVSE_OK;
+}
+
+#define AVSE_DISPATCH_FLAGS_STATE(T, ARGS, HS, ...)                                                 \
+    do {                                                                                           \
+        const bool hz = ARGS.z != nullptr, hd = ARGS.D != nullptr, hb = ARGS.delta_bias != nullptr; \
+        if (hz && hd && hb) launch_fwd_state<T, true, true, true>(ARGS, HS, __VA_ARGS__);          \
+        else if (hz && hd) launch_fwd_state<T, true, true, false>(ARGS, HS, __VA_ARGS__);          \
+        else if (hz && hb) launch_fwd_state<T, true, false, true>(ARGS, HS, __VA_ARGS__);          \
+        else if (hz) launch_fwd_state<T, true, false, false>(ARGS, HS, __VA_ARGS__);               \
+        else if (hd && hb) launch_fwd_state<T, false, true, true>(ARGS, HS, __VA_ARGS__);          \
+        else if (hd) launch_fwd_state<T, false, true, false>(ARGS, HS, __VA_ARGS__);               \
+        else if (hb) launch_fwd_state<T, false, false, true>(ARGS, HS, __VA_ARGS__);               \
+        else launch_fwd_state<T, false, false, false>(ARGS, HS, __VA_ARGS__);                      \
+    } while (0)
+
+int avse_scan_fwd_state(const avse_scan_fwd_state_args* as, avse_stream_t stream) {
+    if (!as) return AVSE_EINVAL;
+    const avse_scan_fwd_args* a = &as->s;
+    if (!a->u || !a->delta || !a->A || !a->B || !a->C) return AVSE_EINVAL;       // x may be NULL: no checkpoints
+    if (a->z ? !a->out_z : !a->out) return AVSE_EINVAL;
+    if (a->reverse || a->out_z_accumulate || a->out_z_max) return AVSE_EINVAL;   // causal inference only
+    int rc = check_mode(a->delta_softplus, a->delta_bias);
+    if (rc) return rc;
+    rc = check_common(a->batch, a->dim, a->seqlen, a->dstate, a->in_dtype);
+    if (rc) return rc;
+    if ((as->h0 && (((uintptr_t)as->h0 | (uintptr_t)(as->h0_bs * 4) | (uintptr_t)(as->h0_ds * 4)) & 15)) ||
+        (as->h_last && (((uintptr_t)as->h_last | (uintptr_t)(as->h_last_bs * 4) | (uintptr_t)(as->h_last_ds * 4)) & 15)))
+        return AVSE_EALIGN;                                                       // 16-B state loads / stores
+    const CarriedState hs{as->h0, as->h0_bs, as->h0_ds, as->h_last, as->h_last_bs, as->h_last_ds};
+    const int nblk_d = (int)((a->dim + CPB - 1) / CPB);
+    const int nblocks = (int)(a->batch * nblk_d);
+    hipStream_t st = (hipStream_t)stream;
+    if (a->in_dtype == AVSE_F32) AVSE_DISPATCH_FLAGS_STATE(float, (*a), hs, nblk_d, nblocks, st);
+    else AVSE_DISPATCH_FLAGS_STATE(bf16_t, (*a), hs, nblk_d, nblocks, st);
+    AVSE_CHECK_LAUNCH();
+    return AVSE_OK;
+}
+
+int avse_ssm_step(const avse_ssm_step_args* a, avse_stream_t stream) {
+    if (!a || !a->state || !a->x || !a->dt || !a->A || !a->B || !a->C || !a->out) return AVSE_EINVAL;
+    if (a->batch <= 0 || a->dim <= 0 || a->batch > 65535) return AVSE_ESHAPE;
+    if (a->dstate != NSTATE) return AVSE_ESHAPE;
+    if (a->dtype != AVSE_F32 && a->dtype != AVSE_BF16) return AVSE_EDTYPE;
+    if (((uintptr_t)a->state | (uintptr_t)(a->state_bs * 4) | (uintptr_t)(a->state_ds * 4) | (uintptr_t)a->A) & 15)
+        return AVSE_EALIGN;
+    const dim3 grid((unsigned)((a->dim + CPB - 1) / CPB), (unsigned)a->batch);
+    hipStream_t st = (hipStream_t)stream;
+    if (a->dtype == AVSE_F32) {
+        if (a->dt_softplus) hipLaunchKernelGGL((step_kernel<float, true>), grid, dim3(THREADS), 0, st, *a);
+        else hipLaunchKernelGGL((step_kernel<float, false>), grid, dim3(THREADS), 0, st, *a);
+    } else {
+        if (a->dt_softplus) hipLaunchKernelGGL((step_kernel<bf16_t, true>), grid, dim3(THREADS), 0, st, *a);
+        else hipLaunchKernelGGL((step_kernel<bf16_t, false>), grid, dim3(THREADS), 0, st, *a);
+    }
     AVSE_CHECK_LAUNCH();
     return AVSE_OK;
 }

@@ -26,5 +26,9 @@ def causal_conv1d_fn(x, weight, bias=None, seq_idx=None, activation=None):
     return _CausalConv1dFn.apply(x, weight, bias, activation in ("silu", "swish"))
 
 
-def causal_conv1d_update(*args, **kwargs):
-    raise NotImplementedError("single-token decode (causal_conv1d_update) is outside the training/eval hot path")
+def causal_conv1d_update(x, conv_state, weight, bias=None, activation=None):
+    """causal-conv1d 1.1.3's single-step update as bimamba.py:335-341 calls it: x (b, d), conv_state (b, d, w) rolled
+    and updated in place, weight (d, w); returns (b, d)."""
+    if activation not in (None, "silu", "swish"):
+        raise NotImplementedError("activation must be None, 'silu' or 'swish'")
+    return _K.causal_conv1d_update(x, conv_state, weight, bias, activation in ("silu", "swish"))

@@ -1,7 +1,10 @@
 """Drop-in for the parts of mamba-ssm 1.1.3.post1 the reference imports."""
 
 
-class Mamba:  # mamba_blocks.py:12 imports it; the bidirectional configs never instantiate it
-    def __init__(self, *a, **k):
-        raise NotImplementedError("unidirectional mamba_ssm.Mamba is not part of the Mamba-TasNet configs "
-                                  "(bidirectional: True in every hparams file)")
+def __getattr__(name):
+    # mamba_blocks.py:12 imports Mamba for its unidirectional (causal) configs: the project's mixer, resolved on
+    # first use so that importing this package alone stays light
+    if name == "Mamba":
+        from avse_challenge_amd.mamba_tasnet import Mamba
+        return Mamba
+    raise AttributeError(name)

@@ -1,2 +1,8 @@
-def selective_state_update(*args, **kwargs):
-    raise NotImplementedError("single-token decode is outside the training/eval hot path")
+"""Drop-in for mamba-ssm 1.1.3's Triton ``selective_state_update`` (single-step decode) on libavse_hip.so."""
+from avse_challenge_amd import kernels as _K
+
+
+def selective_state_update(state, x, dt, A, B, C, D=None, z=None, dt_bias=None, dt_softplus=False):
+    """As bimamba.py:360-362 calls it: state (b, d, n) updated in place; x, dt, z (b, d); A (d, n); B, C (b, n);
+    D, dt_bias (d).  Returns out (b, d)."""
+    return _K.selective_state_update(state, x, dt, A, B, C, D, z, dt_bias, dt_softplus)

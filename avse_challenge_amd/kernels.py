@@ -8,7 +8,8 @@ import functools
 import torch
 
 from . import _lib
-from ._lib import AVSE_BF16, AVSE_F32, ScanBwdArgs, ScanFwdArgs, check, ptr, stream_ptr
+from ._lib import (AVSE_BF16, AVSE_F32, ScanBwdArgs, ScanFwdArgs, ScanFwdStateArgs, SsmStepArgs, check, ptr,
+                   stream_ptr)
 
 NSTATE = 16
 
@@ -130,9 +131,23 @@ def dtproj(w, x, bias=None, softplus=True):
     return out
 
 
+def _ssm_state_arg(t, b, d, dev, what):
+    if (t.dtype != torch.float32 or tuple(t.shape) != (b, d, NSTATE) or t.device != dev or t.stride(2) != 1
+            or t.stride(0) % 4 or t.stride(1) % 4 or t.data_ptr() % 16):
+        raise RuntimeError(f"{what} must be an fp32 ({b}, {d}, {NSTATE}) GPU tensor with unit last stride, 16-B aligned "
+                           f"rows, got {tuple(t.shape)} {t.dtype} strides {t.stride()}")
+    return t
+
+
 def selective_scan_fwd(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, reverse=False,
-                       return_out=True, out_z_acc=None, out_z_max=None):
+                       return_out=True, out_z_acc=None, out_z_max=None, initial_state=None, return_last_state=False,
+                       checkpoints=True):
     """Returns (out, x, out_z|None) — the selective_scan_cuda.fwd contract.
+    Carried state (causal streaming inference, avse_scan_fwd_state; forward time order only): initial_state, an fp32
+    (b, d, 16) tensor (the reference's ssm_state layout) the scan starts from instead of zeros; return_last_state,
+    True or an fp32 (b, d, 16) tensor to write (it may be initial_state itself: in-place update): the state after the
+    last step is appended to the result, (out, x, out_z, last_state); checkpoints=False: no x intermediates are
+    written (x is returned as None; no backward can follow).  Without these three the call is today's.
     reverse=True scans time backwards (== flip(scan(flip(inputs))) with no flip copies).
     return_out=False (only with z): skip writing the pre-gate ``out`` (returned as None); the
     backward recomputes it, so training saves one (b, d, l) write and its activation memory.
@@ -155,8 +170,11 @@ def selective_scan_fwd(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta
     nck = L.avse_scan_n_chunks(l)
     if not return_out and z is None:
         raise RuntimeError("return_out=False needs z (the gated output is then the only result)")
+    stateful = initial_state is not None or return_last_state is not False or not checkpoints
+    if stateful and (reverse or out_z_acc is not None or out_z_max is not None):
+        raise RuntimeError("selective_scan_fwd: carried state runs forwards in time, without out_z_acc / out_z_max")
     out = _bdl_empty(b, d, l, dt, u.device) if return_out else None
-    x = torch.empty((b, d, nck, 2 * NSTATE), device=u.device, dtype=torch.float32)
+    x = torch.empty((b, d, nck, 2 * NSTATE), device=u.device, dtype=torch.float32) if checkpoints else None
     out_z = _bdl_empty(b, d, l, dt, u.device) if z is not None else None
     if out_z_acc is not None:
         if z is None or tuple(out_z_acc.shape) != (b, d, l) or out_z_acc.dtype != dt or out_z_acc.stride(2) != 1 \
@@ -164,7 +182,8 @@ def selective_scan_fwd(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta
             raise RuntimeError("selective_scan_fwd: out_z_acc must be a time-contiguous (b, d, l) tensor of u's dtype "
                                "(and z given)")
         out_z = out_z_acc
-    a = ScanFwdArgs()
+    sa = ScanFwdStateArgs() if stateful else None
+    a = sa.s if stateful else ScanFwdArgs()
     a.batch, a.dim, a.seqlen, a.dstate = b, d, l, NSTATE
     a.in_dtype, a.delta_softplus, a.reverse = _dtype_code(dt), _sp_mode(delta_softplus, delta_bias), int(bool(reverse))
     a.u, a.u_bs, a.u_ds = u.data_ptr(), u.stride(0), u.stride(1)
@@ -181,11 +200,62 @@ def selective_scan_fwd(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta
     a.delta_bias = delta_bias.data_ptr() if delta_bias is not None else None
     if out is not None:
         a.out, a.out_bs, a.out_ds = out.data_ptr(), out.stride(0), out.stride(1)
-    a.x = x.data_ptr()
+    a.x = x.data_ptr() if x is not None else None
+    if stateful:
+        last = None
+        if initial_state is not None:
+            h0 = _ssm_state_arg(initial_state, b, d, u.device, "initial_state")
+            sa.h0, sa.h0_bs, sa.h0_ds = h0.data_ptr(), h0.stride(0), h0.stride(1)
+        if return_last_state is not False:
+            last = (torch.empty((b, d, NSTATE), device=u.device, dtype=torch.float32) if return_last_state is True
+                    else _ssm_state_arg(return_last_state, b, d, u.device, "return_last_state"))
+            sa.h_last, sa.h_last_bs, sa.h_last_ds = last.data_ptr(), last.stride(0), last.stride(1)
+        tap = _tap_begin("avse_scan_fwd_state", u.device)
+        check(L.avse_scan_fwd_state(sa, stream_ptr(u.device)), "avse_scan_fwd_state")
+        _tap_end(tap)
+        return (out, x, out_z, last) if return_last_state is not False else (out, x, out_z)
     tap = _tap_begin("avse_scan_fwd", u.device)
     check(L.avse_scan_fwd(a, stream_ptr(u.device)), "avse_scan_fwd")
     _tap_end(tap)
     return out, x, out_z
+
+
+def selective_state_update(state, x, dt, A, B, C, D=None, z=None, dt_bias=None, dt_softplus=False):
+    """One recurrence step on a cached state (mamba-ssm's selective_state_update, bimamba.py:352-362): state (b, d, 16)
+    fp32 is updated in place; x, dt, z (b, d) and B, C (b, 16) in x's dtype (fp32 or bf16); A (d, 16), D, dt_bias (d)
+    fp32.  Returns out (b, d) in x's dtype."""
+    _need_gpu(state, x, dt, A, B, C, D, z, dt_bias)
+    b, d = x.shape
+    _ssm_state_arg(state, b, d, x.device, "state")
+    dtp = x.dtype
+    code = _dtype_code(dtp)
+    x = _last_contig(x)
+    dt = _last_contig(dt.to(dtp))
+    z = None if z is None else _last_contig(z.to(dtp))
+    B, C = _last_contig(B.to(dtp)), _last_contig(C.to(dtp))
+    if tuple(A.shape) != (d, NSTATE) or tuple(B.shape) != (b, NSTATE) or tuple(C.shape) != (b, NSTATE) \
+            or tuple(dt.shape) != (b, d):
+        raise RuntimeError(f"selective_state_update: A ({d}, {NSTATE}), B / C ({b}, {NSTATE}), dt ({b}, {d}) expected, "
+                           f"got {tuple(A.shape)}, {tuple(B.shape)}, {tuple(C.shape)}, {tuple(dt.shape)}")
+    A = A.float().contiguous()
+    D = None if D is None else D.float().contiguous()
+    dt_bias = None if dt_bias is None else dt_bias.float().contiguous()
+    out = torch.empty((b, d), device=x.device, dtype=dtp)
+    a = SsmStepArgs()
+    a.batch, a.dim, a.dstate, a.dtype, a.dt_softplus = b, d, NSTATE, code, int(bool(dt_softplus))
+    a.state, a.state_bs, a.state_ds = state.data_ptr(), state.stride(0), state.stride(1)
+    a.x, a.x_bs = x.data_ptr(), x.stride(0)
+    a.dt, a.dt_bs = dt.data_ptr(), dt.stride(0)
+    a.A = A.data_ptr()
+    a.B, a.B_bs = B.data_ptr(), B.stride(0)
+    a.C, a.C_bs = C.data_ptr(), C.stride(0)
+    a.D = D.data_ptr() if D is not None else None
+    if z is not None:
+        a.z, a.z_bs = z.data_ptr(), z.stride(0)
+    a.dt_bias = dt_bias.data_ptr() if dt_bias is not None else None
+    a.out, a.out_bs = out.data_ptr(), out.stride(0)
+    check(_lib.lib().avse_ssm_step(a, stream_ptr(x.device)), "avse_ssm_step")
+    return out
 
 
 def selective_scan_bwd(u, delta, A, B, C, D, z, delta_bias, dout, x, out=None, dz=None,
@@ -275,9 +345,19 @@ def selective_scan_bwd(u, delta, A, B, C, D, z, delta_bias, dout, x, out=None, d
 
 # ------------------------------------------------------------------------ causal conv1d
 
-def causal_conv1d_fwd(x, weight, bias=None, silu=False, reverse=False):
-    """out = act(depthwise causal conv(x)) in x's dtype (fp32 or bf16; fp32 weights and arithmetic)."""
-    _need_gpu(x, weight, bias)
+def _conv_state_arg(t, b, d, w, dt, dev):
+    if t.dtype != dt or tuple(t.shape) != (b, d, w) or t.device != dev or t.stride(2) != 1:
+        raise RuntimeError(f"conv_state must be a ({b}, {d}, {w}) {dt} GPU tensor with unit last stride, got "
+                           f"{tuple(t.shape)} {t.dtype} strides {t.stride()}")
+    return t
+
+
+def causal_conv1d_fwd(x, weight, bias=None, silu=False, reverse=False, conv_state=None):
+    """out = act(depthwise causal conv(x)) in x's dtype (fp32 or bf16; fp32 weights and arithmetic).
+    conv_state (streaming inference): a (b, d, w) tensor of x's dtype holding the row's last w inputs, oldest first
+    (the reference's conv_state, bimamba.py:277); the conv takes x[t < 0] from it and it is updated in place to the last
+    w of concat(conv_state, x)."""
+    _need_gpu(x, weight, bias, conv_state)
     dt = x.dtype
     _dtype_code(dt)
     x = _last_contig(x)
@@ -288,9 +368,40 @@ def causal_conv1d_fwd(x, weight, bias=None, silu=False, reverse=False):
     b, d, l = x.shape
     w = weight.shape[1]
     out = _bdl_empty(b, d, l, dt, x.device)
+    if conv_state is not None:
+        if reverse:
+            raise RuntimeError("causal_conv1d_fwd: a carried conv_state runs forwards in time")
+        st = _conv_state_arg(conv_state, b, d, w, dt, x.device)
+        fn = _lib.lib().avse_cconv_fwd_state if dt == torch.float32 else _lib.lib().avse_cconv_fwd_state_bf16
+        check(fn(b, d, l, w, ptr(x), x.stride(0), x.stride(1), ptr(weight), ptr(bias), ptr(out), out.stride(0),
+                 out.stride(1), int(bool(silu)), ptr(st), ptr(st), st.stride(0), st.stride(1), stream_ptr(x.device)),
+              "avse_cconv_fwd_state")
+        return out
     fn = _lib.lib().avse_cconv_fwd if dt == torch.float32 else _lib.lib().avse_cconv_fwd_bf16
     check(fn(b, d, l, w, ptr(x), x.stride(0), x.stride(1), ptr(weight), ptr(bias), ptr(out), out.stride(0),
              out.stride(1), int(bool(silu)), int(bool(reverse)), stream_ptr(x.device)), "avse_cconv_fwd")
+    return out
+
+
+def causal_conv1d_update(x, conv_state, weight, bias=None, silu=False):
+    """One conv step on a cached state (causal-conv1d's causal_conv1d_update, bimamba.py:328-341): conv_state (b, d, w)
+    of x's dtype is rolled left by one in place with x (b, d) as its last column; returns act(bias + sum_k w[:, k]
+    conv_state[:, :, k]) as (b, d) in x's dtype."""
+    _need_gpu(x, conv_state, weight, bias)
+    dt = x.dtype
+    code = _dtype_code(dt)
+    x = _last_contig(x)
+    if weight.dim() == 3:
+        weight = weight.reshape(weight.shape[0], -1)
+    weight = weight.float().contiguous()
+    bias = None if bias is None else bias.float().contiguous()
+    b, d = x.shape
+    w = weight.shape[1]
+    st = _conv_state_arg(conv_state, b, d, w, dt, x.device)
+    out = torch.empty((b, d), device=x.device, dtype=dt)
+    check(_lib.lib().avse_cconv_update(b, d, w, code, ptr(x), x.stride(0), ptr(st), st.stride(0), st.stride(1),
+                                       ptr(weight), ptr(bias), ptr(out), out.stride(0), int(bool(silu)),
+                                       stream_ptr(x.device)), "avse_cconv_update")
     return out
 
 

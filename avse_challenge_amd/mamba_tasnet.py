@@ -355,9 +355,11 @@ class _BiOutProj(torch.autograd.Function):
 
     @staticmethod
     @_FWD
-    def forward(ctx, f, bk, w):
+    def forward(ctx, f, bk, w, scale=0.5):
+        # scale: the 0.5 of the direction average; 1.0 for the unidirectional Mamba's out_proj (bk None, f its output)
         dt = _autocast_dtype()
         y = None
+        ctx.scale = scale
         ctx.two = bk is not None                   # bk None: f already holds the direction sum
         if (bk is not None and dt is None and f.dtype == bk.dtype == w.dtype == torch.float32
                 and f.stride() == bk.stride()):
@@ -372,17 +374,17 @@ class _BiOutProj(torch.autograd.Function):
             out = torch.empty(y.shape[0], y.shape[2], w.shape[0], device=y.device, dtype=torch.float32)
             if _f32_ok(w[None], y.transpose(1, 2), out):
                 ys = K.split_planes(y)
-                K.gemm_f32s(w[None], y.transpose(1, 2), out, 0.5, qs=ys.t())
+                K.gemm_f32s(w[None], y.transpose(1, 2), out, scale, qs=ys.t())
                 ctx.save_for_backward(ys.hi, ys.lo, ys.mb, w)
                 ctx.split = True
                 return out
         ctx.save_for_backward(y, w)
         if dt is None and y.dtype == torch.float32:
             out = _f32_gemm(w[None], y.transpose(1, 2),
-                            torch.empty(y.shape[0], y.shape[2], w.shape[0], device=y.device, dtype=torch.float32), 0.5)
+                            torch.empty(y.shape[0], y.shape[2], w.shape[0], device=y.device, dtype=torch.float32), scale)
             if out is not None:
                 return out
-        wt = 0.5 * w.t()
+        wt = scale * w.t()
         return torch.bmm(y.transpose(1, 2), wt.expand(y.shape[0], *wt.shape))
 
     @staticmethod
@@ -395,18 +397,18 @@ class _BiOutProj(torch.autograd.Function):
             dy = K.bdl_empty(dout.shape[0], w.shape[1], dout.shape[1], torch.float32, dout.device)
             dsp = K.split_planes(dout)                 # (b, l, d_model): shared by the input and the weight gradient
             if _f32_ok(dout, w.t()[None], dy):
-                K.gemm_f32s(dout, w.t()[None], dy, 0.5, ps=dsp)                      # dy = 0.5 W^T dout^T
+                K.gemm_f32s(dout, w.t()[None], dy, ctx.scale, ps=dsp)                # dy = 0.5 W^T dout^T
             else:
-                torch.bmm((0.5 * w.t()).expand(dout.shape[0], *w.t().shape), dout.transpose(1, 2), out=dy)
-            dw = _bsum_split(dsp.t(), ys.t(), w.shape[0], w.shape[1], 0.5)         # 0.5 sum_b dout^T y^T
-            return dy, (dy if ctx.two else None), dw
+                torch.bmm((ctx.scale * w.t()).expand(dout.shape[0], *w.t().shape), dout.transpose(1, 2), out=dy)
+            dw = _bsum_split(dsp.t(), ys.t(), w.shape[0], w.shape[1], ctx.scale)   # 0.5 sum_b dout^T y^T
+            return dy, (dy if ctx.two else None), dw, None
         y, w = ctx.saved_tensors
         dt = _autocast_dtype()
         if dt is not None and dout.dtype != dt:
             dout = dout.to(dt)                          # one cast for both GEMMs below (each would cast its own copy)
-        dy = _wbmm(w.t(), dout.transpose(1, 2), 0.5)                             # (b, d_inner, l)
-        dw = _bsum_mm(dout.transpose(1, 2), y.transpose(1, 2), 0.5)               # (d_model, d_inner)
-        return dy, (dy if ctx.two else None), dw
+        dy = _wbmm(w.t(), dout.transpose(1, 2), ctx.scale)                       # (b, d_inner, l)
+        dw = _bsum_mm(dout.transpose(1, 2), y.transpose(1, 2), ctx.scale)         # (d_model, d_inner)
+        return dy, (dy if ctx.two else None), dw, None
 
 
 class AddRMSNorm(torch.autograd.Function):
@@ -465,11 +467,134 @@ def _direction_stream(device):
     return _STREAMS[device]
 
 
-class BiMambaV2(nn.Module):
+class InferenceParams:
+    """The state carrier of stateful (streaming) inference, as mamba_ssm.utils.generation.InferenceParams: the caller
+    brings it, the mixers keep their (conv_state, ssm_state) in key_value_memory_dict under their layer_idx, and the
+    caller advances seqlen_offset by the frames it has pushed (bimamba.py:184-189,380-406)."""
+
+    def __init__(self, max_seqlen=0, max_batch_size=0, seqlen_offset=0, batch_size_offset=0,
+                 key_value_memory_dict=None, lengths_per_sample=None):
+        self.max_seqlen, self.max_batch_size = max_seqlen, max_batch_size
+        self.seqlen_offset, self.batch_size_offset = seqlen_offset, batch_size_offset
+        self.key_value_memory_dict = {} if key_value_memory_dict is None else key_value_memory_dict
+        self.lengths_per_sample = lengths_per_sample
+
+    def reset(self, max_seqlen=0, max_batch_size=0):
+        self.max_seqlen, self.max_batch_size = max_seqlen, max_batch_size
+        self.seqlen_offset = 0
+        if self.lengths_per_sample is not None:
+            self.lengths_per_sample.zero_()
+
+
+class _StatefulMixer:
+    """Stateful causal inference over a mixer's forward-direction parameters (in_proj, conv1d, x_proj, dt_proj, A_log,
+    D, out_proj), as bimamba.py:176-406: forward(h, inference_params) dispatches here, step() advances one frame.
+    conv_state: (b, d_inner, d_conv) in the activation dtype; ssm_state: (b, d_inner, 16), always fp32 here (the
+    reference allocates it in the parameter dtype).  One extension: a chunk of l > 1 frames at seqlen_offset > 0
+    continues from the cached state through avse_cconv_fwd_state / avse_scan_fwd_state (the reference asserts l == 1
+    there).  No autograd: a backward through carried state is not provided."""
+
+    layer_idx = None
+
+    def allocate_inference_cache(self, batch_size, max_seqlen, dtype=None, **kwargs):
+        dev = self.out_proj.weight.device
+        conv_dtype = self.conv1d.weight.dtype if dtype is None else dtype
+        return (torch.zeros(batch_size, self.d_inner, self.d_conv, device=dev, dtype=conv_dtype),
+                torch.zeros(batch_size, self.d_inner, self.d_state, device=dev, dtype=torch.float32))
+
+    def _get_states_from_cache(self, inference_params, batch_size, initialize_states=False):
+        assert self.layer_idx is not None, "stateful inference needs the mixer's layer_idx"
+        kv = inference_params.key_value_memory_dict
+        if self.layer_idx not in kv:
+            kv[self.layer_idx] = self.allocate_inference_cache(
+                batch_size, 0, dtype=_autocast_dtype() or self.conv1d.weight.dtype)
+        elif initialize_states:
+            for t in kv[self.layer_idx]:
+                t.zero_()
+        return kv[self.layer_idx]
+
+    @torch.no_grad()
+    def step(self, hidden_states, conv_state, ssm_state):
+        """(b, 1, d_model) -> ((b, 1, d_model), conv_state, ssm_state); the states are updated in place
+        (avse_cconv_update, avse_ssm_step)."""
+        assert hidden_states.shape[1] == 1, "step() advances one frame; chunks go through forward()"
+        r, n = self.dt_rank, self.d_state
+        xz = F.linear(hidden_states.squeeze(1), self.in_proj.weight)             # (b, 2 di)
+        x, z = xz.chunk(2, dim=-1)
+        x = K.causal_conv1d_update(x, conv_state, self.conv1d.weight, self.conv1d.bias, silu=True)
+        x_db = F.linear(x, self.x_proj.weight)                                   # (b, r + 2n)
+        dt = F.linear(x_db[:, :r], self.dt_proj.weight)                          # the bias goes in with the softplus
+        y = K.selective_state_update(ssm_state, x, dt, -torch.exp(self.A_log.float()), x_db[:, r:r + n],
+                                     x_db[:, r + n:], self.D.float(), z, self.dt_proj.bias.float(), True)
+        return F.linear(y, self.out_proj.weight).unsqueeze(1), conv_state, ssm_state
+
+    @torch.no_grad()
+    def _stateful_forward(self, h, inference_params):
+        b, l, _ = h.shape
+        conv_state, ssm_state = self._get_states_from_cache(inference_params, b)
+        first = inference_params.seqlen_offset == 0
+        if not first and l == 1:
+            return self.step(h, conv_state, ssm_state)[0]
+        if first:                                   # the reference's prefill starts from zero states (bimamba.py:277)
+            conv_state.zero_()
+        r = self.dt_rank
+        xz = _wbmm(self.in_proj.weight, h.transpose(1, 2))                       # (b, 2 di, l)
+        if xz.dtype != conv_state.dtype:
+            raise RuntimeError(f"conv_state is {conv_state.dtype} but the activations are {xz.dtype}: allocate the "
+                               "inference cache in the activation dtype (bf16 under autocast)")
+        x, z = xz.chunk(2, dim=1)
+        conv_out = K.causal_conv1d_fwd(x, self.conv1d.weight, self.conv1d.bias, silu=True, conv_state=conv_state)
+        x_dblT = _wbmm(self.x_proj.weight, conv_out)                             # (b, r + 2n, l)
+        delta, bias, mode = _delta(self.dt_proj.weight, x_dblT[:, :r], self.dt_proj.bias.float())
+        res = K.selective_scan_fwd(conv_out, delta, -torch.exp(self.A_log.float()), x_dblT[:, r:r + NSTATE],
+                                   x_dblT[:, r + NSTATE:], self.D.float(), z, bias, mode, return_out=False,
+                                   initial_state=None if first else ssm_state, return_last_state=ssm_state,
+                                   checkpoints=False)
+        return F.linear(res[2].transpose(1, 2), self.out_proj.weight)            # (b, l, d_model), unscaled
+
+
+class Mamba(_StatefulMixer, nn.Module):
+    """The unidirectional (causal) mixer with the parameters and keys of mamba-ssm's Mamba (mamba_blocks.py:128):
+    in_proj, conv1d, x_proj, dt_proj, A_log, D, out_proj; init as BiMambaV2's forward direction."""
+
+    def __init__(self, d_model, d_state=16, d_conv=4, expand=2, layer_idx=None, dt_min=0.001, dt_max=0.1,
+                 dt_init_floor=1e-4):
+        super().__init__()
+        assert d_state == NSTATE, "the HIP scan is built for d_state 16 (all reference configs)"
+        self.d_model, self.d_state, self.d_conv, self.layer_idx = d_model, d_state, d_conv, layer_idx
+        self.d_inner = expand * d_model
+        self.dt_rank = math.ceil(d_model / 16)
+        di, r, n = self.d_inner, self.dt_rank, d_state
+        self.in_proj = nn.Linear(d_model, 2 * di, bias=False)
+        self.conv1d = nn.Conv1d(di, di, d_conv, groups=di, padding=d_conv - 1, bias=True)
+        self.x_proj = nn.Linear(di, r + 2 * n, bias=False)
+        self.dt_proj = nn.Linear(r, di, bias=True)
+        self.A_log = nn.Parameter(torch.log(torch.arange(1, n + 1, dtype=torch.float32)).repeat(di, 1))
+        self.D = nn.Parameter(torch.ones(di))
+        self.out_proj = nn.Linear(di, d_model, bias=False)
+        std = self.dt_rank ** -0.5                      # dt init as bimamba.py:101-120
+        with torch.no_grad():
+            nn.init.uniform_(self.dt_proj.weight, -std, std)
+            dt = torch.exp(torch.rand(di) * (math.log(dt_max) - math.log(dt_min)) + math.log(dt_min))
+            dt = dt.clamp(min=dt_init_floor)
+            self.dt_proj.bias.copy_(dt + torch.log(-torch.expm1(-dt)))
+
+    def forward(self, h, inference_params=None):               # (b, l, d_model)
+        if inference_params is not None:
+            return self._stateful_forward(h, inference_params)
+        xz = _InProj.apply(h, self.in_proj.weight)
+        y = MambaInnerNoOutProj.apply(xz, self.conv1d.weight, self.conv1d.bias, self.x_proj.weight, self.dt_proj.weight,
+                                      -torch.exp(self.A_log.float()), self.D.float(), self.dt_proj.bias.float(), False)
+        return _BiOutProj.apply(y, None, self.out_proj.weight, 1.0)          # no direction average: unscaled
+
+
+class BiMambaV2(_StatefulMixer, nn.Module):
     """bimamba.Mamba(bimamba_type='v2', if_devide_out=True): same parameters and init."""
 
-    def __init__(self, d_model, d_state=16, d_conv=4, expand=2, dt_min=0.001, dt_max=0.1, dt_init_floor=1e-4):
+    def __init__(self, d_model, d_state=16, d_conv=4, expand=2, dt_min=0.001, dt_max=0.1, dt_init_floor=1e-4,
+                 layer_idx=None):
         super().__init__()
+        self.layer_idx = layer_idx
         assert d_state == NSTATE, "the HIP scan is built for d_state 16 (all reference configs)"
         self.d_model, self.d_state, self.d_conv = d_model, d_state, d_conv
         self.d_inner = expand * d_model
@@ -496,7 +621,11 @@ class BiMambaV2(nn.Module):
                 dt = dt.clamp(min=dt_init_floor)
                 proj.bias.copy_(dt + torch.log(-torch.expm1(-dt)))
 
-    def forward(self, h):                                        # (b, l, d_model)
+    def forward(self, h, inference_params=None):                 # (b, l, d_model)
+        if inference_params is not None:
+            # as the reference (bimamba.py:184-189,271-315): with a state carrier only the forward direction runs,
+            # statefully, and its out_proj is not halved
+            return self._stateful_forward(h, inference_params)
         xz = _InProj.apply(h, self.in_proj.weight)                               # (b, 2di, l), no copy
         A = -torch.exp(self.A_log.float())
         A_b = -torch.exp(self.A_b_log.float())
@@ -541,22 +670,38 @@ class Block(nn.Module):
         self.mixer = mixer
         self.norm = RMSNorm(d_model, eps)
 
-    def forward(self, h, residual=None):
+    def forward(self, h, residual=None, inference_params=None):
         y, residual = AddRMSNorm.apply(h, residual, self.norm.weight, self.norm.eps, True)
+        if inference_params is not None:
+            return self.mixer(y, inference_params=inference_params), residual
         return self.mixer(y), residual
+
+    def allocate_inference_cache(self, batch_size, max_seqlen, dtype=None, **kwargs):
+        return self.mixer.allocate_inference_cache(batch_size, max_seqlen, dtype=dtype, **kwargs)
 
 
 class MambaBlocksSequential(nn.Module):
-    def __init__(self, n_mamba, d_model, d_state=16, expand=2, d_conv=4, eps=1e-5):
+    """bidirectional=False: causal blocks of the unidirectional Mamba (mamba_blocks.py:128), which can stream."""
+
+    def __init__(self, n_mamba, d_model, d_state=16, expand=2, d_conv=4, eps=1e-5, bidirectional=True):
         super().__init__()
-        self.layers = nn.Sequential(*[Block(d_model, BiMambaV2(d_model, d_state, d_conv, expand), eps)
-                                      for _ in range(n_mamba)])
+        self.bidirectional = bidirectional
+
+        def mixer(i):
+            if bidirectional:
+                return BiMambaV2(d_model, d_state, d_conv, expand, layer_idx=i)
+            return Mamba(d_model, d_state, d_conv, expand, layer_idx=i)
+        self.layers = nn.Sequential(*[Block(d_model, mixer(i), eps) for i in range(n_mamba)])
         self.norm_f = RMSNorm(d_model, eps)
 
-    def forward(self, x):
+    def allocate_inference_cache(self, batch_size, max_seqlen, dtype=None, **kwargs):
+        return {i: layer.allocate_inference_cache(batch_size, max_seqlen, dtype=dtype, **kwargs)
+                for i, layer in enumerate(self.layers)}
+
+    def forward(self, x, inference_params=None):
         h, res = x, None
         for layer in self.layers:
-            h, res = layer(h, res)
+            h, res = layer(h, res, inference_params)
         return AddRMSNorm.apply(h, res, self.norm_f.weight, self.norm_f.eps)[0]
 
 
@@ -586,18 +731,21 @@ class Conv1x1(nn.Module):
 
 
 class MaskNet(nn.Module):
-    def __init__(self, enc_dim, bot_dim, n_spk=2, n_mamba=16, d_model=256, d_state=16, expand=2, d_conv=4):
+    def __init__(self, enc_dim, bot_dim, n_spk=2, n_mamba=16, d_model=256, d_state=16, expand=2, d_conv=4,
+                 bidirectional=True):
         super().__init__()
         self.n_spk = n_spk
         self.layer_norm = ChannelwiseLayerNorm(enc_dim)
         self.bottleneck_conv1x1 = Conv1x1(enc_dim, bot_dim)
-        self.mamba_net = MambaBlocksSequential(n_mamba, d_model, d_state, expand, d_conv)
+        self.mamba_net = MambaBlocksSequential(n_mamba, d_model, d_state, expand, d_conv, bidirectional=bidirectional)
         self.mask_conv1x1 = Conv1x1(bot_dim, n_spk * enc_dim)
 
-    def forward(self, mixture_w):                      # (M, N, K) -> (n_spk, M, N, K)
+    def forward(self, mixture_w, inference_params=None):     # (M, N, K) -> (n_spk, M, N, K)
         x = mixture_w.permute(0, 2, 1)
         Bn, L, D = x.shape
-        y = self.mask_conv1x1(self.mamba_net(self.bottleneck_conv1x1(self.layer_norm(x))))
+        h = self.bottleneck_conv1x1(self.layer_norm(x))
+        h = self.mamba_net(h) if inference_params is None else self.mamba_net(h, inference_params)
+        y = self.mask_conv1x1(h)
         return F.relu(y.reshape(Bn, L, self.n_spk, D).permute(2, 0, 3, 1))
 
 
@@ -629,11 +777,13 @@ class Decoder(nn.ConvTranspose1d):
 class MambaTasNet(nn.Module):
     """Encoder / MaskNet / Decoder with compute_forward semantics (train_wsj0mix.py:86-111)."""
 
-    def __init__(self, N=512, kernel_size=16, n_mamba=32, n_spk=2, d_state=16, expand=2, d_conv=4):
+    def __init__(self, N=512, kernel_size=16, n_mamba=32, n_spk=2, d_state=16, expand=2, d_conv=4,
+                 bidirectional=True):
         super().__init__()
         self.num_spks = n_spk
+        self.bidirectional = bidirectional
         self.encoder = Encoder(kernel_size, N)
-        self.masknet = MaskNet(N, N, n_spk, n_mamba, N, d_state, expand, d_conv)
+        self.masknet = MaskNet(N, N, n_spk, n_mamba, N, d_state, expand, d_conv, bidirectional=bidirectional)
         self.decoder = Decoder(N, 1, kernel_size, stride=kernel_size // 2, bias=False)
 
     def forward(self, mix):                            # (B, T) -> (B, T, n_spk)
@@ -645,6 +795,68 @@ class MambaTasNet(nn.Module):
         if T > est.shape[1]:
             return F.pad(est, (0, 0, 0, T - est.shape[1]))
         return est[:, :T, :]
+
+
+class StreamingSeparator:
+    """Chunk-by-chunk separation with a causal MambaTasNet (bidirectional=False).
+
+    push(chunk) takes (B, C) samples, C a positive multiple of the hop (kernel_size // 2), and returns the (B, C', n_spk)
+    output samples that are final; flush() returns the tail; reset() clears the state.  For T >= kernel_size with
+    (T - kernel_size) % hop == 0, the concatenation of all pushes and the flush equals model(mix).
+
+    Carried between pushes: the last hop input samples (the encoder's frames overlap by half a window, so the first
+    push yields one frame fewer, possibly none), the last hop output samples per source (the second half of the newest
+    decoder frame, still waiting for its overlap-add partner) and every layer's (conv_state, ssm_state).  The
+    channel-wise LayerNorm, the 1x1 convolutions and the RMSNorms act per frame and need no state.
+
+    Algorithmic latency is one encoder window (kernel_size samples): output sample t needs the frame that covers
+    t .. t + hop, i.e. input up to t + kernel_size - 1 at the latest; nothing later is ever read."""
+
+    def __init__(self, model, batch):
+        if getattr(model, "bidirectional", True):
+            raise ValueError("StreamingSeparator needs a causal model: MambaTasNet(..., bidirectional=False)")
+        self.model, self.batch = model, batch
+        self.k = model.encoder.conv1d.kernel_size[0]
+        self.hop = model.encoder.conv1d.stride[0]
+        self.reset()
+
+    def reset(self):
+        self.params = InferenceParams(max_batch_size=self.batch)
+        self.in_tail = None          # (B, hop): the newest hop input samples
+        self.out_tail = None         # (B, hop, n_spk): second halves of the newest frames, not yet overlap-added
+
+    @torch.no_grad()
+    def push(self, chunk):
+        B, C = chunk.shape
+        if B != self.batch or C <= 0 or C % self.hop:
+            raise ValueError(f"push takes ({self.batch}, C) with C a positive multiple of the hop {self.hop}, got "
+                             f"{tuple(chunk.shape)}")
+        m, hop, k = self.model, self.hop, self.k
+        x = chunk if self.in_tail is None else torch.cat([self.in_tail, chunk], dim=1)
+        self.in_tail = x[:, -hop:].clone()
+        n_frames = x.shape[1] // hop - 1
+        if n_frames <= 0:
+            return chunk.new_zeros(B, 0, m.num_spks)
+        mix_w = m.encoder(x)                                              # (B, N, n_frames)
+        est_mask = m.masknet(mix_w, self.params)
+        self.params.seqlen_offset += n_frames
+        sep_h = mix_w.unsqueeze(0) * est_mask
+        # decoder frames (B, k, n_frames) per source; overlap-add over the new frames plus the carried half frame
+        est = torch.stack([m.decoder(sep_h[i]) for i in range(m.num_spks)], dim=-1)     # (B, (n_frames + 1) hop, S)
+        if self.out_tail is not None:
+            est[:, :hop] += self.out_tail
+        self.out_tail = est[:, -hop:].clone()
+        return est[:, :-hop]
+
+    @torch.no_grad()
+    def flush(self):
+        """The last hop output samples (empty before the first frame); the separator is reset afterwards."""
+        tail = self.out_tail
+        if tail is None:
+            ref = self.model.decoder.weight
+            tail = ref.new_zeros(self.batch, 0, self.model.num_spks)
+        self.reset()
+        return tail
 
 
 MAMBA_TASNET_SIZES = {"XS": dict(N=128, n_mamba=16), "S": dict(N=256, n_mamba=16),

@@ -105,6 +105,44 @@ int64_t avse_scan_bwd_workspace_bytes(int64_t batch, int64_t dim, int64_t seqlen
 int avse_scan_fwd(const avse_scan_fwd_args* a, avse_stream_t stream);
 int avse_scan_bwd(const avse_scan_bwd_args* a, avse_stream_t stream);
 
+/* Forward scan with carried state (causal streaming inference; no backward).  Replaces
+ * selective_scan_fn(..., return_last_state=True) continued from a cached ssm_state (bimamba.py:299-313,
+ * selective_scan_interface.py:83-88).  s: the fields of avse_scan_fwd with these differences: s.x may be NULL (no
+ * checkpoints are written: an inference call has no backward to restart), and s.reverse, s.out_z_accumulate and
+ * s.out_z_max must be 0 / NULL (AVSE_EINVAL).  h0: the state before the first step, (b, d, 16) fp32 with the given
+ * batch / channel strides (the reference's ssm_state layout), or NULL for zeros.  h_last: receives the state after
+ * the last step (or NULL); it may alias h0 (in-place update: each lane reads the states it later writes).  Both
+ * 16-B aligned with strides that are multiples of 4 (AVSE_EALIGN). */
+typedef struct {
+    avse_scan_fwd_args s;
+    const float* h0;    int64_t h0_bs, h0_ds;
+    float* h_last;      int64_t h_last_bs, h_last_ds;
+} avse_scan_fwd_state_args;
+int avse_scan_fwd_state(const avse_scan_fwd_state_args* a, avse_stream_t stream);
+
+/* One recurrence step on a cached state: the selective_state_update(state, x, dt, A, B, C, D, z, dt_bias,
+ * dt_softplus) contract of mamba-ssm 1.1.3 as called at bimamba.py:360-362, semantics bimamba.py:352-358:
+ *   dt' = softplus(dt + dt_bias) (dt_softplus != 0; else dt + dt_bias); state = state exp(dt' A) + dt' x B;
+ *   out = (sum_n state C + D x) silu(z).
+ * state (b, d, 16) fp32, updated in place (16-B aligned, strides multiples of 4); x, dt, z, out (b, d) of dtype
+ * (AVSE_F32 / AVSE_BF16) with d contiguous and the given batch strides; B, C (b, 16) of dtype; A (d, 16) fp32
+ * contiguous, 16-B aligned; D, dt_bias (d) fp32 or NULL; z NULL = no gate.  batch <= 65535. */
+typedef struct {
+    int64_t batch, dim, dstate;
+    int32_t dtype, dt_softplus;
+    float* state;       int64_t state_bs, state_ds;
+    const void* x;      int64_t x_bs;
+    const void* dt;     int64_t dt_bs;
+    const float* A;
+    const void* B;      int64_t B_bs;
+    const void* C;      int64_t C_bs;
+    const float* D;
+    const void* z;      int64_t z_bs;
+    const float* dt_bias;
+    void* out;          int64_t out_bs;
+} avse_ssm_step_args;
+int avse_ssm_step(const avse_ssm_step_args* a, avse_stream_t stream);
+
 /* dt_proj with the scan's softplus in the epilogue.  Replaces
  *   delta = delta_proj_weight @ x_dbl[:, :delta_rank].t()      selective_scan_interface.py:187
  * followed by selective_scan_cuda's per-element softplus(delta + delta_bias) (selective_scan_ref :110-112):
@@ -156,6 +194,31 @@ int avse_cconv_bwd_bf16(int64_t batch, int64_t dim, int64_t seqlen, int64_t widt
                         float* dweight, float* dbias,
                         int32_t silu, int32_t reverse, float* workspace, int32_t dx_accumulate, uint32_t* dx_max,
                         avse_stream_t stream);
+/* Causal conv with carried left context (streaming inference).  conv_state: (b, d, w) in the activation dtype, the
+ * last w inputs of the row, oldest first (the reference's conv_state, bimamba.py:277,328-329), w contiguous, batch /
+ * channel strides st_bs / st_ds shared by state_in and state_out.  The conv reads x[t < 0] from state_in (NULL =
+ * zeros) and state_out (or NULL) receives the last w of concat(state_in, x), also for l < w.  state_out may alias
+ * state_in: the thread that reads a row's old state is the one that writes its new state.  reverse is not taken. */
+int avse_cconv_fwd_state(int64_t batch, int64_t dim, int64_t seqlen, int64_t width,
+                         const float* x, int64_t x_bs, int64_t x_ds,
+                         const float* weight, const float* bias,
+                         float* out, int64_t out_bs, int64_t out_ds, int32_t silu,
+                         const float* state_in, float* state_out, int64_t st_bs, int64_t st_ds,
+                         avse_stream_t stream);
+int avse_cconv_fwd_state_bf16(int64_t batch, int64_t dim, int64_t seqlen, int64_t width,
+                              const uint16_t* x, int64_t x_bs, int64_t x_ds,
+                              const float* weight, const float* bias,
+                              uint16_t* out, int64_t out_bs, int64_t out_ds, int32_t silu,
+                              const uint16_t* state_in, uint16_t* state_out, int64_t st_bs, int64_t st_ds,
+                              avse_stream_t stream);
+/* One conv step on a cached state: the causal_conv1d_update(x, conv_state, weight, bias, activation) contract of
+ * causal-conv1d 1.1.3 as called at bimamba.py:335-341, semantics bimamba.py:328-333: conv_state (b, d, w) is rolled
+ * left by one, x (b, d) becomes its last column, out[b, d] = act(bias[d] + sum_k w[d, k] conv_state[b, d, k]).
+ * x / out: d contiguous, batch strides x_bs / out_bs.  dtype AVSE_F32 or AVSE_BF16 (x, conv_state, out). */
+int avse_cconv_update(int64_t batch, int64_t dim, int64_t width, int32_t dtype,
+                      const void* x, int64_t x_bs, void* conv_state, int64_t st_bs, int64_t st_ds,
+                      const float* weight, const float* bias, void* out, int64_t out_bs, int32_t silu,
+                      avse_stream_t stream);
 
 /* ---------------------------------------------------------------- add + RMSNorm -------
  * Replaces the Block pre-norm of Mamba-TasNet/modules/mamba/bimamba.py:447-451
