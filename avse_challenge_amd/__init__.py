@@ -6,7 +6,8 @@ reference's operator / module surfaces:
                  lip Conv3d weight gradient, PReLU, fused PReLU+gLN, depthwise dilated conv1d, BatchNorm+act,
                  max pooling, LSTM recurrence)
   layers         autograd modules over those kernels (PReLU, LipConv3d, prelu_gln, dwconv1d, dwconv_prelu_gln,
-                 bn_act (BatchNorm -> [+res] -> act), maxpool3d, HipLSTM)
+                 bn_act (BatchNorm -> [+res] -> act), maxpool3d, bn_act_pool_frames (the lip front-ends' fused
+                 BatchNorm3d -> act -> MaxPool3d -> channels-last frames), HipLSTM)
   dropin         importable stand-ins for selective_scan_cuda / causal_conv1d(_cuda) / mamba_ssm
   mamba_tasnet   Mamba-TasNet separator (Encoder, MaskNet of BiMamba v2 blocks, Decoder)
   avse1          avse1 AVNet with the STFT front-end / iSTFT back-end on the GPU

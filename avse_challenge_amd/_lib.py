@@ -179,6 +179,11 @@ SIGNATURES = {
     # BatchNorm backward from the input-gradient conv's epilogue rows (model.py:199-215, utils/resnet.py:40-67)
     "avse_bnact_bwd_rows": (c_i32, [c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_vp,
                                     c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
+    # the lip front-end chain BatchNorm3d -> act -> MaxPool3d -> channels-last frames (model.py:29-34, :46-50)
+    "avse_bnpool_supported": (c_i32, [c_i64] * 5),
+    "avse_bnpool_rows": (c_i64, [c_i64] * 5),
+    "avse_bnpool_fwd": (c_i32, [c_i64] * 5 + [c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_f32, c_f32] + [c_vp] * 7),
+    "avse_bnpool_bwd": (c_i32, [c_i64] * 5 + [c_vp] * 6 + [c_i32, c_vp, c_i32, c_i32] + [c_vp] * 7),
     "avse_dconv_bn_rows": (c_i64, [c_i64] * 4),
     "avse_dconv_dgrad_bn": (c_i32, [c_i64] * 4 + [c_vp] * 8 + [c_i32, c_i32, c_vp, c_vp]),
     "avse_sconv_bn_rows": (c_i64, [c_i64] * 4),

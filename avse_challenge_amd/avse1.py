@@ -20,8 +20,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import kernels as K
-from .layers import (DilatedConv2d, HipLSTM, LipConv3d, PointwiseConv2d, PReLU, TrunkConv2d, bn_act, conv1x1_to4,
-                     frames_nhwc, maxpool3d, time_conv1d, time_major_4d)
+from .layers import (DilatedConv2d, HipLSTM, LipConv3d, PointwiseConv2d, PReLU, TrunkConv2d, bn_act,
+                     bn_act_pool_frames, conv1x1_to4, maxpool3d, time_conv1d, time_major_4d)
 
 STFT_BINS, NUM_STFT_FRAMES, NUM_FRAMES, SAMPLES = 257, 376, 75, 48000
 
@@ -158,12 +158,13 @@ class VisualFeatNet(nn.Module):           # model.py:17-58
     def forward(self, lips):              # (B, 3, T, H, W) raw 0..255 (uint8 as stored, or float) -> (B, T, 512)
         Bn = lips.shape[0]
         conv, bn, act, pool = self.frontend3D
-        x = maxpool3d(bn_act(conv(lips), bn, act), pool)
-        Tn, C, H, W = x.shape[2], x.shape[1], x.shape[3], x.shape[4]
-        if self.channels_last:            # (B, C, T, H, W) -> (B*T, H, W, C) in memory, viewed as NCHW
-            x = frames_nhwc(x)
+        x = conv(lips)
+        Tn = x.shape[2]
+        if self.channels_last:            # (B, C, T, H, W) -> (B*T, H, W, C) in memory, viewed as NCHW: one fused chain
+            x = bn_act_pool_frames(x, bn, act, pool, bn_act)
         else:
-            x = x.transpose(1, 2).reshape(Bn * Tn, C, H, W)
+            x = maxpool3d(bn_act(x, bn, act), pool)
+            x = x.transpose(1, 2).reshape(Bn * Tn, x.shape[1], x.shape[3], x.shape[4])
         x = self.trunk(x).view(Bn, Tn, -1)
         return self.tcn(x)
 

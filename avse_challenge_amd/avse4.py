@@ -21,8 +21,8 @@ import torch.nn.functional as F
 
 from . import kernels as K
 from . import losses
-from .layers import (LipConv3d, PointwiseConv2d, TrunkConv2d, _PReLUFn, bn_act, dwconv1d, dwconv_prelu_gln, frames_nhwc,
-                     maxpool3d, prelu_gln)
+from .layers import (LipConv3d, PointwiseConv2d, TrunkConv2d, _PReLUFn, bn_act, bn_act_pool_frames, dwconv1d,
+                     dwconv_prelu_gln, maxpool3d, prelu_gln)
 
 NORM_MEAN, NORM_STD = 0.4161, 0.1688
 
@@ -343,11 +343,11 @@ class VisualFrontend(nn.Module):
     def forward(self, x):                                   # (B, 1, T, 112, 112) -> (B, T, 512)
         bsz = x.shape[0]
         conv, bn, _, pool = self.frontend3D
-        y = maxpool3d(bn_act(conv((x - NORM_MEAN) / NORM_STD), bn, "relu"), pool)
+        y = conv((x - NORM_MEAN) / NORM_STD)
         if self.channels_last:
-            y = frames_nhwc(y)
+            y = bn_act_pool_frames(y, bn, "relu", pool, bn_act)
         else:
-            y = y.transpose(1, 2)
+            y = maxpool3d(bn_act(y, bn, "relu"), pool).transpose(1, 2)
             y = y.reshape(y.shape[0] * y.shape[1], y.shape[2], y.shape[3], y.shape[4])
         return self.resnet(y).reshape(bsz, -1, 512)
 

@@ -19,7 +19,8 @@
 // HBM traffic per element: forward 4 B (statistics) + 8 B (apply, +4 with a residual); backward 8 B
 // (partials) + 12 B (apply); with a residual 12 + 4 (dres written) and 12.  Where dy comes from a split-fp16
 // input-gradient convolution whose epilogue wrote the per-tile sums (bnact_cols.h, avse_bnact_bwd_rows) the backward's
-// partials pass is not run: 12 B (apply) + 4 B (x, read in the producer's epilogue).
+// partials pass is not run: 12 B (apply) + 4 B (x, read in the producer's epilogue).  The lip front-ends' chain
+// BatchNorm3d -> act -> MaxPool3d -> channels-last frames has kernels of its own (namespace pool below).
 #include <algorithm>
 
 #include "bnact_cols.h"
@@ -446,6 +447,200 @@ __global__ __launch_bounds__(THREADS) void bwd_apply_kernel(Geo g, const float* 
     if (dxmax) block_max_out(m, dxmax);                  // workgroup-uniform condition
 }
 
+// ---- the lip front-end chain BatchNorm3d -> ReLU / PReLU -> MaxPool3d((1, 3, 3), (1, 2, 2), (0, 1, 1)) -> frames as
+// channels-last (avse1 VisualFeatNet.forward, avse4 VisualFrontend.forward), in one pass forward and two backward
+// The unfused chain writes the activated (B, C, T, H, W) tensor only for the pool to read it back, the pooled planes
+// only for the frame transpose to read them back, and the un-pooled gradient (three quarters of it zeros) only for the
+// two BatchNorm backward passes to read it.  Here a workgroup owns (b, t, 64 channels, a band of RB pooled rows):
+//   forward   reads x along each channel plane (the float4 + scalar pattern of maxpool.hip's fwd_k3s2p1_w4_kernel, the
+//             rows between neighbouring windows and bands re-read from cache), forms z = act(ColConst::preact(x)) per
+//             loaded element, pools it with that kernel's scan order and comparison, writes the argmax byte in
+//             maxpool.hip's plane layout and transposes only the pooled tile through LDS: whole 256-B pixel rows of
+//             the (B T, Ho, Wo, C) frames.
+//   backward  stages the band's RB + 1 rows of the channels-last pooled gradient in LDS, forms each 2 x 4 input
+//             block's un-pooled gradient from its 6 candidate windows in maxpool.hip's (ho, wo) order (the value the
+//             unfused chain wrote to memory) and feeds it to the BatchNorm backward: the sums pass writes one row of
+//             [3][C] per workgroup (chan_partial_kernel / bwd_combine finish them as for avse_bnact_bwd_rows:
+//             deterministic, no atomics), the apply pass writes dx and publishes max |dx|.
+// A thread group of GL = 8 lanes walks one channel's band, so the channel constants are per-thread registers and the
+// 8 lanes read 128 contiguous bytes of a plane row.
+namespace pool {
+
+constexpr int CT = 64, RB = 4, LP = CT + 1, GL = 8, MAXW = 96;
+
+struct PGeo {
+    int B, C, T, H, W, Ho, Wo, bands, ctiles;
+    uint32_t mq;                                          // j / (W / 4) = (j * mq) >> 16 for j < 128 (W / 4 <= 24)
+};
+
+struct Blk {
+    int band, ct, b, t, r0, nr;
+    int64_t bt;
+    __device__ inline Blk(const PGeo& p) {
+        band = (int)(blockIdx.x % p.bands);
+        ct = (int)((blockIdx.x / p.bands) % p.ctiles);
+        bt = blockIdx.x / (p.bands * p.ctiles);
+        b = (int)(bt / p.T);
+        t = (int)(bt - (int64_t)b * p.T);
+        r0 = band * RB;
+        nr = min(RB, p.Ho - r0);
+    }
+};
+
+template <int ACT>
+__global__ __launch_bounds__(THREADS) void fwd_kernel(PGeo p, const float* __restrict__ x,
+                                                      const float* __restrict__ stats, const float* __restrict__ gamma,
+                                                      const float* __restrict__ beta, const float* __restrict__ alpha,
+                                                      int alpha_n, float* __restrict__ y, uint8_t* __restrict__ idx) {
+    extern __shared__ float tile[];                       // [nr * Wo pooled pixels][LP]
+    const Blk k(p);
+    const int Pb = p.W >> 2, items = k.nr * Pb;
+    const int sub = threadIdx.x / GL, l8 = threadIdx.x % GL;
+    for (int pass = 0; pass < CT * GL / THREADS; ++pass) {
+        const int cl = pass * (THREADS / GL) + sub, c = k.ct * CT + cl;
+        ColConst<1, ACT> cc;
+        cc.load_channel(0, c, stats, gamma, beta, alpha, alpha_n);
+        const int64_t pl = ((int64_t)k.b * p.C + c) * p.T + k.t;
+        const float* xc = x + pl * p.H * p.W;
+        uint8_t* ic = idx + pl * p.Ho * p.Wo;
+        for (int j = l8; j < items; j += GL) {
+            const int r = (int)(((uint32_t)j * p.mq) >> 16), wp = j - r * Pb, ho = k.r0 + r;
+            const float* xp = xc + 4 * wp;
+            float v[3][5];
+#pragma unroll
+            for (int kh = 0; kh < 3; ++kh) {
+                const int h = 2 * ho - 1 + kh;
+                const bool ok = h >= 0 && h < p.H;
+                const float4 q = ok ? *reinterpret_cast<const float4*>(xp + h * p.W) : make_float4(0.f, 0.f, 0.f, 0.f);
+                v[kh][0] = (ok && wp > 0) ? xp[h * p.W - 1] : 0.f;
+                v[kh][1] = q.x; v[kh][2] = q.y; v[kh][3] = q.z; v[kh][4] = q.w;
+#pragma unroll
+                for (int e = 0; e < 5; ++e) v[kh][e] = act_fwd<ACT>(cc.preact(v[kh][e], 0), cc.al[0]);
+            }
+            // the scan of maxpool.hip fwd_k3s2p1_w4_kernel: first maximum, strict '>', a NaN taken
+            const int kh0 = ho == 0 ? 1 : 0;
+            const int hmax = min(3, p.H - (2 * ho - 1));
+            float best[2];
+            int arg[2];
+#pragma unroll
+            for (int o = 0; o < 2; ++o) {
+                const int kw0 = (wp == 0 && o == 0) ? 1 : 0;
+                best[o] = -__builtin_inff();
+                arg[o] = (kh0 << 4) | kw0;
+#pragma unroll
+                for (int kh = 0; kh < 3; ++kh) {
+                    if (kh < kh0 || kh >= hmax) continue;
+#pragma unroll
+                    for (int kw = 0; kw < 3; ++kw) {
+                        if (kw < kw0) continue;
+                        const float e = v[kh][2 * o + kw];
+                        if (e > best[o] || e != e) {
+                            best[o] = e;
+                            arg[o] = (kh << 4) | kw;
+                        }
+                    }
+                }
+            }
+            tile[(r * p.Wo + 2 * wp) * LP + cl] = best[0];
+            tile[(r * p.Wo + 2 * wp + 1) * LP + cl] = best[1];
+            *reinterpret_cast<uint16_t*>(ic + ho * p.Wo + 2 * wp) = (uint16_t)(arg[0] | (arg[1] << 8));
+        }
+    }
+    __syncthreads();
+    float* yb = y + ((k.bt * p.Ho + k.r0) * p.Wo) * p.C + k.ct * CT;
+    for (int q = threadIdx.x; q < k.nr * p.Wo * CT; q += THREADS) yb[(int64_t)(q / CT) * p.C + q % CT] = tile[(q / CT) * LP + q % CT];
+}
+
+template <int ACT, bool APPLY>
+__global__ __launch_bounds__(THREADS) void bwd_kernel(PGeo p, const float* __restrict__ x, const float* __restrict__ g,
+                                                      const uint8_t* __restrict__ idx, const float* __restrict__ stats,
+                                                      const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                      const float* __restrict__ alpha, int alpha_n,
+                                                      const float* __restrict__ kbuf, float* __restrict__ rows,
+                                                      float* __restrict__ dx, uint32_t* __restrict__ dxmax) {
+    extern __shared__ float tile[];                       // [ngr * Wo pooled pixels][LP]: pooled rows r0 .. r0 + ngr - 1
+    const Blk k(p);
+    const int ngr = min(RB + 1, p.Ho - k.r0);
+    const float* gb = g + ((k.bt * p.Ho + k.r0) * p.Wo) * p.C + k.ct * CT;
+    for (int q = threadIdx.x; q < ngr * p.Wo * CT; q += THREADS) tile[(q / CT) * LP + q % CT] = gb[(int64_t)(q / CT) * p.C + q % CT];
+    __syncthreads();
+    const int Nq = p.W >> 2, items = k.nr * Nq;
+    const int sub = threadIdx.x / GL, l8 = threadIdx.x % GL;
+    float mx = 0.f;
+    for (int pass = 0; pass < CT * GL / THREADS; ++pass) {
+        const int cl = pass * (THREADS / GL) + sub, c = k.ct * CT + cl;
+        ColConst<1, ACT> cc;
+        cc.load_channel(0, c, stats, gamma, beta, alpha, alpha_n);
+        const float k1 = APPLY ? kbuf[2 * c] : 0.f, k2 = APPLY ? kbuf[2 * c + 1] : 0.f;
+        const int64_t pl = ((int64_t)k.b * p.C + c) * p.T + k.t;
+        const uint8_t* ic = idx + pl * p.Ho * p.Wo;
+        float s[3] = {0.f, 0.f, 0.f};
+        for (int j = l8; j < items; j += GL) {
+            const int r = (int)(((uint32_t)j * p.mq) >> 16), nq = j - r * Nq, m = k.r0 + r;
+            // input rows 2m, 2m + 1, columns 4nq .. 4nq + 3: windows ho = m, m + 1, wo = 2nq .. 2nq + 2; a window's
+            // argmax lies at (2 dh - 1 + kh, 2 kk - 1 + kw) from (2m, 4nq)
+            float gd[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+            for (int dh = 0; dh < 2; ++dh) {
+                const int ho = m + dh;
+                if (ho >= p.Ho) break;
+                const uint8_t* ip = ic + ho * p.Wo + 2 * nq;
+                const uint32_t a01 = *reinterpret_cast<const uint16_t*>(ip);
+                const bool has2 = 2 * nq + 2 < p.Wo;
+                const uint32_t a2 = has2 ? ip[2] : 0xffu;
+                const float* tp = tile + ((r + dh) * p.Wo + 2 * nq) * LP + cl;
+#pragma unroll
+                for (int kk = 0; kk < 3; ++kk) {
+                    if (kk == 2 && !has2) break;
+                    const int a = kk == 0 ? (int)(a01 & 0xff) : (kk == 1 ? (int)(a01 >> 8) : (int)a2);
+                    const float v = tp[kk * LP];
+                    const int di = 2 * dh - 1 + (a >> 4), dj = 2 * kk - 1 + (a & 15);
+#pragma unroll
+                    for (int i = dh; i < 2; ++i)
+#pragma unroll
+                        for (int e = (kk == 0 ? 0 : 2 * kk - 1); e <= min(3, 2 * kk + 1); ++e)
+                            if (di == i && dj == e) gd[i][e] += v;
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const int64_t o = pl * p.H * p.W + (int64_t)(2 * m + i) * p.W + 4 * nq;
+                float v[4];
+                vld<4>::ld(x + o, v);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float z = cc.preact(v[e], 0);
+                    const float dz = act_bwd<ACT>(z, gd[i][e], cc.al[0]);
+                    const float xh = cc.xhat(v[e], 0);
+                    if constexpr (APPLY) {
+                        v[e] = cc.a[0] * (dz - k1 - xh * k2);
+                        mx = fmaxf(mx, fabsf(v[e]));
+                    } else {
+                        s[0] += dz;
+                        s[1] = fmaf(dz, xh, s[1]);
+                        if (ACT == ACT_PRELU && !(z > 0.f)) s[2] = fmaf(gd[i][e], z, s[2]);
+                    }
+                }
+                if constexpr (APPLY) vld<4>::st(dx + o, v);
+            }
+        }
+        if constexpr (!APPLY) {
+            const int64_t row = k.bt * p.bands + k.band;
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                float v = s[q];
+                for (int o = 1; o < GL; o <<= 1) v += __shfl_xor(v, o, 64);
+                if (l8 == 0) rows[(row * 3 + q) * p.C + c] = v;
+            }
+        }
+    }
+    if constexpr (APPLY) {
+        if (dxmax) block_max_out(mx, dxmax);            // workgroup-uniform condition
+    }
+}
+
+}  // namespace pool
+
 // ---- host side
 inline int pow2ceil(int64_t v) {
     int p = 1;
@@ -527,19 +722,14 @@ int64_t avse_bnact_workspace_bytes(int64_t N, int64_t C, int64_t S) {
     return 4 * (4 * nrb * C * S + 2 * C) + 16 + 8 * (int64_t)C * MAXG * 4;
 }
 
-static int bnact_fwd_impl(int64_t N, int64_t C, int64_t S, const float* x, const float* res, const float* gamma,
-                          const float* beta, int32_t act, const float* alpha, int32_t alpha_n, int32_t training, float eps,
-                          float momentum, float* running_mean, float* running_var, float* stats, float* y,
-                          float* workspace, uint32_t* y_max, bool qout, hipStream_t st) {
-    if (!x || !y || !stats || !workspace || (act == ACT_PRELU && !alpha)) return AVSE_EINVAL;
-    if (!training && (!running_mean || !running_var)) return AVSE_EINVAL;
-    if (!shape_ok(N, C, S) || act < ACT_NONE || act > ACT_PRELU) return AVSE_ESHAPE;
-    if (act == ACT_PRELU && alpha_n != 1 && alpha_n != C) return AVSE_ESHAPE;
-    if (training && N * S < 2) return AVSE_ESHAPE;       // as torch: more than one value per channel
-    const int V = ((C * S) % 4 == 0 && al16(x) && al16(y) && (!res || al16(res)) && al16(workspace)) ? 4 : 1;
-    if (qout && (!y_max || !training || res || S != 1 || C % 64 || V != 4)) return AVSE_ESHAPE;
-    const Geo g = make_geo(N, C, S, V);
+// the forward's statistics: training: stats_kernel -> chan_partial_kernel -> stats_combine (batch statistics, the running
+// update); eval: the running statistics.  y_max (may be null) is reset in stream order (qout: takes the split bound)
+static int launch_stats(const Geo& g, int V, const float* x, const float* gamma, const float* beta, int32_t act,
+                        const float* alpha, int32_t alpha_n, int32_t training, float eps, float momentum,
+                        float* running_mean, float* running_var, float* stats, float* workspace, uint32_t* y_max,
+                        bool qout, hipStream_t st) {
     const dim3 grid(g.tiles, g.nrb);
+    const int64_t C = g.C;
     if (training) {
         if (V == 4) hipLaunchKernelGGL((stats_kernel<4, true>), grid, dim3(THREADS), 0, st, g, x, workspace);
         else hipLaunchKernelGGL((stats_kernel<1, true>), grid, dim3(THREADS), 0, st, g, x, workspace);
@@ -557,6 +747,25 @@ static int bnact_fwd_impl(int64_t N, int64_t C, int64_t S, const float* x, const
                            running_var, eps, stats, y_max);
     }
     AVSE_CHECK_LAUNCH();
+    return AVSE_OK;
+}
+
+static int bnact_fwd_impl(int64_t N, int64_t C, int64_t S, const float* x, const float* res, const float* gamma,
+                          const float* beta, int32_t act, const float* alpha, int32_t alpha_n, int32_t training, float eps,
+                          float momentum, float* running_mean, float* running_var, float* stats, float* y,
+                          float* workspace, uint32_t* y_max, bool qout, hipStream_t st) {
+    if (!x || !y || !stats || !workspace || (act == ACT_PRELU && !alpha)) return AVSE_EINVAL;
+    if (!training && (!running_mean || !running_var)) return AVSE_EINVAL;
+    if (!shape_ok(N, C, S) || act < ACT_NONE || act > ACT_PRELU) return AVSE_ESHAPE;
+    if (act == ACT_PRELU && alpha_n != 1 && alpha_n != C) return AVSE_ESHAPE;
+    if (training && N * S < 2) return AVSE_ESHAPE;       // as torch: more than one value per channel
+    const int V = ((C * S) % 4 == 0 && al16(x) && al16(y) && (!res || al16(res)) && al16(workspace)) ? 4 : 1;
+    if (qout && (!y_max || !training || res || S != 1 || C % 64 || V != 4)) return AVSE_ESHAPE;
+    const Geo g = make_geo(N, C, S, V);
+    const dim3 grid(g.tiles, g.nrb);
+    const int rc = launch_stats(g, V, x, gamma, beta, act, alpha, alpha_n, training, eps, momentum, running_mean,
+                                running_var, stats, workspace, y_max, qout, st);
+    if (rc != AVSE_OK) return rc;
     if (qout)
         dispatch_q<ApplyQK>::run(act, grid, st, g, x, res, (const float*)stats, gamma, beta, alpha, (int)alpha_n, y, y_max);
     else
@@ -687,6 +896,97 @@ int avse_bnact_bwd_rows(int64_t N, int64_t C, int64_t rows, const float* x, cons
     else
         dispatch<BwdApplyK>::run(4, act, false, grid, st, g, x, dy, (const float*)nullptr, stats, gamma, beta, alpha,
                                  (int)alpha_n, (const float*)kbuf, dx, dx_max);
+    AVSE_CHECK_LAUNCH();
+    return AVSE_OK;
+}
+
+// ---- the fused lip front-end chain (namespace pool above)
+static bool pool_geo(pool::PGeo& p, int64_t B, int64_t C, int64_t T, int64_t H, int64_t W) {
+    if (B <= 0 || C <= 0 || T <= 0 || H < 2 || W < 4 || C % pool::CT || H % 2 || W % 4 || W > pool::MAXW) return false;
+    if (H > (1 << 20) || !shape_ok(B, C, T * H * W)) return false;
+    p.B = (int)B; p.C = (int)C; p.T = (int)T; p.H = (int)H; p.W = (int)W;
+    p.Ho = (int)(H / 2); p.Wo = (int)(W / 2);
+    p.bands = (p.Ho + pool::RB - 1) / pool::RB;
+    p.ctiles = (int)(C / pool::CT);
+    p.mq = 65536u / (uint32_t)(W / 4) + 1u;
+    return B * T * p.ctiles * p.bands < (1LL << 31) && B * T * p.bands < (1 << 23);   // chan_partial_kernel: cnt < 2^23
+}
+
+int32_t avse_bnpool_supported(int64_t B, int64_t C, int64_t T, int64_t H, int64_t W) {
+    pool::PGeo p;
+    return pool_geo(p, B, C, T, H, W) ? 1 : 0;
+}
+
+int64_t avse_bnpool_rows(int64_t B, int64_t C, int64_t T, int64_t H, int64_t W) {
+    pool::PGeo p;
+    return pool_geo(p, B, C, T, H, W) ? B * T * p.bands : 0;
+}
+
+int avse_bnpool_fwd(int64_t B, int64_t C, int64_t T, int64_t H, int64_t W, const float* x, const float* gamma,
+                    const float* beta, int32_t act, const float* alpha, int32_t alpha_n, int32_t training, float eps,
+                    float momentum, float* running_mean, float* running_var, float* stats, float* y, uint8_t* idx,
+                    float* workspace, avse_stream_t stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!x || !y || !idx || !stats || !workspace || (act == ACT_PRELU && !alpha)) return AVSE_EINVAL;
+    if (!training && (!running_mean || !running_var)) return AVSE_EINVAL;
+    pool::PGeo p;
+    if (!pool_geo(p, B, C, T, H, W) || act < ACT_NONE || act > ACT_PRELU) return AVSE_ESHAPE;
+    if (act == ACT_PRELU && alpha_n != 1 && alpha_n != C) return AVSE_ESHAPE;
+    if (!al16(x) || !al16(y) || !al16(workspace) || ((uintptr_t)idx & 1)) return AVSE_EALIGN;
+    const Geo g = make_geo(B, C, T * H * W, 4);
+    const int rc = launch_stats(g, 4, x, gamma, beta, act, alpha, alpha_n, training, eps, momentum, running_mean,
+                                running_var, stats, workspace, nullptr, false, st);
+    if (rc != AVSE_OK) return rc;
+    const dim3 grid((unsigned)(B * T * p.ctiles * p.bands));
+    const size_t lds = sizeof(float) * pool::RB * p.Wo * pool::LP;
+#define AVSE_POOL_FWD(AA) \
+    hipLaunchKernelGGL((pool::fwd_kernel<AA>), grid, dim3(THREADS), lds, st, p, x, (const float*)stats, gamma, beta, alpha, \
+                       (int)alpha_n, y, idx)
+    if (act == ACT_NONE) AVSE_POOL_FWD(ACT_NONE);
+    else if (act == ACT_RELU) AVSE_POOL_FWD(ACT_RELU);
+    else AVSE_POOL_FWD(ACT_PRELU);
+#undef AVSE_POOL_FWD
+    AVSE_CHECK_LAUNCH();
+    return AVSE_OK;
+}
+
+int avse_bnpool_bwd(int64_t B, int64_t C, int64_t T, int64_t H, int64_t W, const float* x, const float* g,
+                    const uint8_t* idx, const float* stats, const float* gamma, const float* beta, int32_t act,
+                    const float* alpha, int32_t alpha_n, int32_t training, float* dx, float* dgamma, float* dbeta,
+                    float* dalpha_c, float* workspace, uint32_t* dx_max, avse_stream_t stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (!x || !g || !idx || !stats || !dx || !workspace || (act == ACT_PRELU && (!alpha || !dalpha_c))) return AVSE_EINVAL;
+    pool::PGeo p;
+    if (!pool_geo(p, B, C, T, H, W) || act < ACT_NONE || act > ACT_PRELU) return AVSE_ESHAPE;
+    if (act == ACT_PRELU && alpha_n != 1 && alpha_n != C) return AVSE_ESHAPE;
+    if (!al16(x) || !al16(g) || !al16(dx) || !al16(workspace) || ((uintptr_t)idx & 1)) return AVSE_EALIGN;
+    const int64_t rows = B * T * p.bands;
+    // the per-channel reduction and the combine see the chain as a channels-last (B T H W, C) BatchNorm with `rows` rows
+    Geo gc = make_geo(B * T * H * W, C, 1, 4);
+    Geo gr = gc;
+    gr.nrb = (int)rows;
+    float* kbuf = workspace + rows_floats(rows, C, 3);
+    double* fin = reinterpret_cast<double*>(((uintptr_t)(kbuf + 2 * C) + 15) & ~(uintptr_t)15);
+    const int G = chan_groups(gr);
+    const dim3 grid((unsigned)(B * T * p.ctiles * p.bands));
+    const size_t lds = sizeof(float) * (pool::RB + 1) * p.Wo * pool::LP;
+#define AVSE_POOL_BWD(AA, AP) \
+    hipLaunchKernelGGL((pool::bwd_kernel<AA, AP>), grid, dim3(THREADS), lds, st, p, x, g, idx, stats, gamma, beta, alpha, \
+                       (int)alpha_n, (const float*)kbuf, workspace, dx, dx_max)
+    if (act == ACT_NONE) AVSE_POOL_BWD(ACT_NONE, false);
+    else if (act == ACT_RELU) AVSE_POOL_BWD(ACT_RELU, false);
+    else AVSE_POOL_BWD(ACT_PRELU, false);
+    AVSE_CHECK_LAUNCH();
+    hipLaunchKernelGGL((chan_partial_kernel<3>), dim3((unsigned)C, G), dim3(THREADS), 0, st, gr, (const float*)workspace,
+                       fin, (uint32_t*)nullptr);
+    AVSE_CHECK_LAUNCH();
+    hipLaunchKernelGGL(bwd_combine, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, st, gc, (const double*)fin, G,
+                       (int)training, dgamma, dbeta, dalpha_c, kbuf, dx_max, 0, stats, gamma);
+    AVSE_CHECK_LAUNCH();
+    if (act == ACT_NONE) AVSE_POOL_BWD(ACT_NONE, true);
+    else if (act == ACT_RELU) AVSE_POOL_BWD(ACT_RELU, true);
+    else AVSE_POOL_BWD(ACT_PRELU, true);
+#undef AVSE_POOL_BWD
     AVSE_CHECK_LAUNCH();
     return AVSE_OK;
 }

@@ -1291,6 +1291,63 @@ def bnact_bwd_rows(x, dy, stats, gamma, beta, act, alpha, training, rows, ws, q_
     return dx, None, dgamma, dbeta, dalpha
 
 
+# ------------------------------------------------------------------------ BatchNorm3d -> act -> MaxPool3d -> frames
+
+def bnpool_ok(x, k, s, p):
+    """True where the fused lip front-end chain (csrc/bnact.hip, namespace pool) takes x (B, C, T, H, W): fp32,
+    contiguous, 3 x 3 / stride 2 / pad 1 pooling, C % 64 == 0, H even, W % 4 == 0 (and W <= 96)."""
+    return (x.is_cuda and x.dim() == 5 and x.dtype == torch.float32 and x.is_contiguous() and x.data_ptr() % 16 == 0
+            and tuple(k) == (3, 3) and tuple(s) == (2, 2) and tuple(p) == (1, 1)
+            and _lib.lib().avse_bnpool_supported(*x.shape) == 1)
+
+
+def bnact_pool_frames_fwd(x, gamma, beta, running_mean, running_var, training, momentum, eps, act=ACT_NONE, alpha=None):
+    """frames_nhwc(maxpool(act(BatchNorm(x)))) of the lip front-ends in one pass after the statistics (bnpool_ok(x)):
+    -> (y (B T, C, Ho, Wo) in channels-last memory, idx (B, C, T, Ho, Wo) uint8, stats as bnact_fwd's)."""
+    _need_gpu(x)
+    B, C, T, H, W = x.shape
+    y = torch.empty((B * T, H // 2, W // 2, C), device=x.device, dtype=torch.float32)
+    idx = torch.empty((B, C, T, H // 2, W // 2), device=x.device, dtype=torch.uint8)
+    stats = torch.empty((C, 4), device=x.device, dtype=torch.float32)
+    L = _lib.lib()
+    ws = torch.empty((L.avse_bnact_workspace_bytes(B, C, T * H * W) + 3) // 4, device=x.device, dtype=torch.float32)
+    a = alpha.float().contiguous() if alpha is not None else None
+    check(L.avse_bnpool_fwd(B, C, T, H, W, ptr(x), _opt(gamma), _opt(beta), int(act), _opt(a),
+                            a.numel() if a is not None else 0, int(bool(training)), float(eps), float(momentum),
+                            _opt(running_mean), _opt(running_var), ptr(stats), ptr(y), ptr(idx), ptr(ws),
+                            stream_ptr(x.device)), "avse_bnpool_fwd")
+    return y.permute(0, 3, 1, 2), idx, stats
+
+
+def _bnpool_ws(rows, C, device):
+    return torch.empty((_lib.lib().avse_bnact_rows_workspace_bytes(rows, C, 3) + 3) // 4, device=device,
+                       dtype=torch.float32)
+
+
+def bnact_pool_frames_bwd(x, g, idx, stats, gamma, beta, act, alpha, training):
+    """Backward of bnact_pool_frames_fwd: g the gradient of its output (B T, C, Ho, Wo), read as channels-last frames
+    -> (dx (B, C, T, H, W) carrying its max |dx|, dgamma, dbeta, dalpha (alpha's shape) or None)."""
+    _need_gpu(x, g, idx, stats)
+    B, C, T, H, W = x.shape
+    g = g.float().permute(0, 2, 3, 1).contiguous()           # a view for a channels-last gradient
+    dx = torch.empty_like(x)
+    dgamma = torch.empty((C,), device=x.device, dtype=torch.float32)
+    dbeta = torch.empty((C,), device=x.device, dtype=torch.float32)
+    a = alpha.float().contiguous() if alpha is not None else None
+    dalpha_c = torch.empty((C,), device=x.device, dtype=torch.float32) if a is not None else None
+    L = _lib.lib()
+    ws = _bnpool_ws(L.avse_bnpool_rows(B, C, T, H, W), C, x.device)
+    dxmax = torch.empty(1, device=x.device, dtype=torch.int32)
+    check(L.avse_bnpool_bwd(B, C, T, H, W, ptr(x), ptr(g), ptr(idx), ptr(stats), _opt(gamma), _opt(beta), int(act),
+                            _opt(a), a.numel() if a is not None else 0, int(bool(training)), ptr(dx), ptr(dgamma),
+                            ptr(dbeta), _opt(dalpha_c), ptr(ws), ptr(dxmax), stream_ptr(x.device)), "avse_bnpool_bwd")
+    _set_absmax(dx, dxmax)
+    dalpha = None
+    if a is not None:
+        dalpha = (dalpha_c if a.numel() == C else dalpha_c.sum().reshape(1)).view_as(alpha)
+    return dx, dgamma, dbeta, dalpha
+
+
 # ------------------------------------------------------------------------ PReLU -> gLN (avse4)
 
 def prelu_gln_fwd(x, alpha, gamma, beta, eps=1e-8):

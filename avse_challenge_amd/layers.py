@@ -7,6 +7,7 @@ dwconv_prelu_gln  the avse4 TCN's dwconv -> PReLU -> gLN as two fused passes eac
 PReLU        nn.PReLU(num_parameters): fwd + fused dx / slope-gradient bwd kernels (NCS and channels-last)
 bn_act       act(nn.BatchNorm{1,2,3}d(x) [+ res]) with act None / ReLU / PReLU, two passes each way
 maxpool3d    nn.MaxPool3d((1, k, k), (1, s, s), (0, p, p)) of the lip front-ends (byte argmax, gather backward)
+bn_act_pool_frames  the lip front-ends' BatchNorm3d -> act -> MaxPool3d -> channels-last frames as one fused chain
 HipLSTM      nn.LSTM(..., num_layers=1, batch_first=True[, bidirectional]) whose recurrence is one HIP launch
              per direction (avse1 FusionNet, avse2 DPRNN)
 DilatedConv2d  nn.Conv2d(64, 64, 5, padding=2d, dilation=d) of the avse1 AudioFeatNet: weight gradient on the
@@ -145,6 +146,14 @@ def bn_act(x, bn, act=None, res=None, folded_bias=None, q_fwd=False, q_bwd=False
         return y
     if not x.is_cuda:
         raise RuntimeError("bn_act runs on the GPU kernels only")
+    training, code, alpha, rm, rv, momentum = _bn_module_args(bn, act)
+    return _BNActFn.apply(x.float(), bn.weight, bn.bias, alpha, res, rm, rv, training, momentum, bn.eps, code,
+                          bool(q_fwd), bool(q_bwd))
+
+
+def _bn_module_args(bn, act):
+    """The kernels' arguments of an nn.BatchNorm{1,2,3}d and its activation; counts the batch in train mode (one call
+    per forward) -> (training, act code, alpha, running_mean, running_var, momentum)."""
     training = bn.training or not bn.track_running_stats
     if bn.training and bn.track_running_stats:
         if bn.momentum is None:
@@ -158,8 +167,7 @@ def bn_act(x, bn, act=None, res=None, folded_bias=None, q_fwd=False, q_bwd=False
         code, alpha = K.ACT_PRELU, act.weight
     rm = bn.running_mean if bn.track_running_stats else None
     rv = bn.running_var if bn.track_running_stats else None
-    return _BNActFn.apply(x.float(), bn.weight, bn.bias, alpha, res, rm, rv, training,
-                          bn.momentum if bn.momentum is not None else 0.0, bn.eps, code, bool(q_fwd), bool(q_bwd))
+    return training, code, alpha, rm, rv, bn.momentum if bn.momentum is not None else 0.0
 
 
 class _MaxPoolPlanesFn(torch.autograd.Function):
@@ -180,14 +188,20 @@ class _MaxPoolPlanesFn(torch.autograd.Function):
 def maxpool3d(x, pool):
     """nn.MaxPool3d `pool` with a (1, KH, KW) window, stride (1, SH, SW), padding (0, PH, PW) (the lip front-ends)
     on the HIP plane kernels (csrc/maxpool.hip); any other configuration raises."""
+    k, s, p = _plane_pool_cfg(pool)
+    if not x.is_cuda:
+        raise RuntimeError("maxpool3d runs on the GPU kernels only")
+    return _MaxPoolPlanesFn.apply(x, k, s, p)
+
+
+def _plane_pool_cfg(pool):
+    """(KH, KW), (SH, SW), (PH, PW) of an nn.MaxPool3d over (H, W) planes; any other configuration raises."""
     k, s, p = (tuple(v) if isinstance(v, (tuple, list)) else (v,) * 3 for v in (pool.kernel_size, pool.stride,
                                                                                  pool.padding))
     d = pool.dilation if isinstance(pool.dilation, (tuple, list)) else (pool.dilation,) * 3
     if k[0] != 1 or s[0] != 1 or p[0] != 0 or tuple(d) != (1, 1, 1) or pool.ceil_mode or pool.return_indices:
         raise NotImplementedError(f"maxpool3d: only (1, KH, KW) windows, got {pool}")
-    if not x.is_cuda:
-        raise RuntimeError("maxpool3d runs on the GPU kernels only")
-    return _MaxPoolPlanesFn.apply(x, k[1:], s[1:], p[1:])
+    return k[1:], s[1:], p[1:]
 
 
 def _conv3d_fwd_folded(x, w, padding):
@@ -362,6 +376,45 @@ def frames_nhwc(x):
     if x.is_cuda and x.dtype == torch.float32:
         return _FramesNHWC.apply(x)
     return x.permute(0, 2, 3, 4, 1).reshape(B * T, H, W, C).permute(0, 3, 1, 2)
+
+
+class _BNActPoolFramesFn(torch.autograd.Function):
+    """frames_nhwc(maxpool3d(bn_act(x))) of the lip front-ends as one pass after the statistics and two backward
+    (csrc/bnact.hip, namespace pool): the activated tensor and the un-pooled gradient are never written."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, alpha, running_mean, running_var, training, momentum, eps, act):
+        y, idx, stats = K.bnact_pool_frames_fwd(x, gamma, beta, running_mean, running_var, training, momentum, eps, act,
+                                                alpha)
+        ctx.save_for_backward(x, idx, stats, gamma, beta, alpha)
+        ctx.act, ctx.training = act, training
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, idx, stats, gamma, beta, alpha = ctx.saved_tensors
+        dx, dgamma, dbeta, dalpha = K.bnact_pool_frames_bwd(x, g, idx, stats, gamma, beta, ctx.act, alpha, ctx.training)
+        return (dx, dgamma if ctx.needs_input_grad[1] else None, dbeta if ctx.needs_input_grad[2] else None,
+                dalpha if ctx.needs_input_grad[3] else None, None, None, None, None, None, None)
+
+
+def bn_act_pool_frames(x, bn, act, pool, bn_act_fn=None):
+    """frames_nhwc(maxpool3d(bn_act(x, bn, act), pool)): x (B, C, T, H, W) -> (B*T, C, Ho, Wo) channels-last, with
+    bn_act's duties (running statistics, num_batches_tracked, training / eval).  The fused kernels take 3 x 3 / stride
+    2 / pad 1 pooling of a contiguous fp32 x with C % 64 == 0, even H and W % 4 == 0 (K.bnpool_ok); everything else
+    runs the three functions.
+    bn_act_fn: the caller's bn_act.  The fused chain never materialises the activation, so a caller whose bn_act has
+    been wrapped or replaced (the models' activation probes: a wrapper that records or imposes every activation's sign
+    pattern) gets the three functions, with its own bn_act."""
+    k, s, p = _plane_pool_cfg(pool)
+    if not x.is_cuda:
+        raise RuntimeError("bn_act_pool_frames runs on the GPU kernels only")
+    if bn_act_fn is not None and bn_act_fn is not bn_act:
+        return frames_nhwc(maxpool3d(bn_act_fn(x, bn, act), pool))
+    if not K.bnpool_ok(x, k, s, p):
+        return frames_nhwc(maxpool3d(bn_act(x, bn, act), pool))
+    training, code, alpha, rm, rv, momentum = _bn_module_args(bn, act)
+    return _BNActPoolFramesFn.apply(x, bn.weight, bn.bias, alpha, rm, rv, training, momentum, bn.eps, code)
 
 
 # AudioFeatNet.conv1 on csrc/conv1.hip (direct HBM-streaming kernels) for frames of >= 128 bins; narrower ones: the

@@ -375,6 +375,27 @@ int avse_bnact_bwd_rows(int64_t N, int64_t C, int64_t rows, const float* x, cons
                         const float* gamma, const float* beta, int32_t act, const float* alpha, int32_t alpha_n,
                         int32_t training, float* dx, float* dgamma, float* dbeta, float* dalpha_c, float* workspace,
                         uint32_t* dx_max, int32_t q_out, avse_stream_t stream);
+/* The lip front-end chain BatchNorm3d -> none / ReLU / PReLU -> MaxPool3d((1, 3, 3), (1, 2, 2), (0, 1, 1)) -> frames in
+ * channels-last memory (baseline/avse1/model.py:29-34 and :46-50, avse4 VisualFrontend) as one pass forward and two
+ * backward, in place of avse_bnact_fwd -> avse_maxpool2d_fwd -> avse_transpose_cp and their backwards: neither the
+ * activated tensor nor the un-pooled gradient is written.  x, dx: (B, C, T, H, W) contiguous; y, g (the gradient of
+ * y): (B T, H / 2, W / 2, C) contiguous; idx: one argmax byte per pooled element, (B, C, T, H / 2, W / 2) with
+ * avse_maxpool2d_fwd's encoding; stats, the running statistics, act, alpha, training as avse_bnact_fwd / _bwd.  The
+ * forward's statistics launches are avse_bnact_fwd's, y and idx are bit-identical to the three calls; dx, dgamma,
+ * dbeta, dalpha_c agree with theirs to the rounding of a re-ordered fp32 sum (deterministic, no atomics); dx_max (may
+ * be null): max |dx| as avse_bnact_bwd's.  Needs C % 64 == 0, H even, W % 4 == 0, W <= 96, 16-B aligned pointers
+ * (avse_bnpool_supported: 1 / 0; other shapes return AVSE_ESHAPE).  workspace: forward
+ * avse_bnact_workspace_bytes(B, C, T H W), backward avse_bnact_rows_workspace_bytes(avse_bnpool_rows(...), C, 3). */
+int32_t avse_bnpool_supported(int64_t B, int64_t C, int64_t T, int64_t H, int64_t W);
+int64_t avse_bnpool_rows(int64_t B, int64_t C, int64_t T, int64_t H, int64_t W);
+int avse_bnpool_fwd(int64_t B, int64_t C, int64_t T, int64_t H, int64_t W, const float* x, const float* gamma,
+                    const float* beta, int32_t act, const float* alpha, int32_t alpha_n, int32_t training, float eps,
+                    float momentum, float* running_mean, float* running_var, float* stats, float* y, uint8_t* idx,
+                    float* workspace, avse_stream_t stream);
+int avse_bnpool_bwd(int64_t B, int64_t C, int64_t T, int64_t H, int64_t W, const float* x, const float* g,
+                    const uint8_t* idx, const float* stats, const float* gamma, const float* beta, int32_t act,
+                    const float* alpha, int32_t alpha_n, int32_t training, float* dx, float* dgamma, float* dbeta,
+                    float* dalpha_c, float* workspace, uint32_t* dx_max, avse_stream_t stream);
 
 /* ---------------------------------------------------------------- max pooling over planes -------
  * nn.MaxPool3d((1, KH, KW), (1, SH, SW), (0, PH, PW)) of the lip front-ends (avse1 model.py:29-34, avse4
