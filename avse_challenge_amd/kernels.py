@@ -868,13 +868,30 @@ def convf_bwd(x, w, dy, need_dx=True, need_dw=True):
 
 # ------------------------------------------------------------------------ ResNet trunk 3x3 Conv2d (split fp16 MFMA)
 
+SCONV_NPOS_MAX = 720          # sconv.hip NPOS_MAX: input positions one forward stage holds in LDS
+
+
+def sconv_fwd_fits(w, cout, stride):
+    """True when avse_sconv_fwd's pixel tile over rows of w input pixels fits its LDS stage (sconv.hip fwd_npos against
+    NPOS_MAX, which avse_sconv_fwd answers with "unsupported shape"): narrow rows under a 512-pixel tile do not, e.g.
+    w = 9 at stride 2 into 64 channels."""
+    tm = 512 if cout % 128 else 256
+    wo = (w - 1) // stride + 1
+    rs = stride * wo + 2
+    rows = (tm - 1 + wo - 1) // wo + 1
+    return (rows * rs + 15) // 16 * 16 <= SCONV_NPOS_MAX
+
+
 def sconv_ok(x, cout, stride):
     """True when csrc/sconv.hip takes Conv2d(cin, cout, 3, stride, padding=1, bias=False) on x: (N, cin, H, W) fp32 GPU
-    tensor, cin and cout multiples of 64, stride 1 or 2, the pixel counts inside the kernels' 32-bit offsets."""
+    tensor, cin and cout multiples of 64, stride 1 or 2, the pixel counts inside the kernels' 32-bit offsets, and the
+    forward's tile (at stride 1 also its input gradient's: the same kernel with cin and cout swapped) inside LDS."""
     if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and stride in (1, 2)):
         return False
     n, cin, h, w = x.shape
     if cin % 64 or cout % 64 or n * h * w * max(cin, cout) * 4 >= (1 << 31) - 4096:
+        return False
+    if not sconv_fwd_fits(w, cout, stride) or (stride == 1 and not sconv_fwd_fits(w, cin, 1)):
         return False
     return _lib.lib().avse_sconv_wgrad_workspace_bytes(n, h, w, cin, cout, stride) > 0
 
@@ -1796,8 +1813,9 @@ def split_planes(t):
 def split_rows8(t):
     """t (b, r, c) fp32 with stride(2) == 1 -> Split whose planes are (b, r, c) views of (b, r, cp) storage, cp = c
     rounded up to a multiple of 8 (csrc/projgemm.hip avse_split16_planes_to): an operand of avse_gemm_f32s read along c
-    or along r whatever c is (the avse4 (B, C, K) activations, K = 3999).  The pad columns are never written; the GEMM
-    only reads them into output rows it does not store (along r) or into the zeroed tail of its last k-stage (along c)."""
+    or along r whatever c is (the avse4 (B, C, K) activations, K = 3999).  The pad columns are written as zeros: the
+    time-chunked weight gradient (gemm_f32s_time_chunks) sums over them; the 16 elements of slack are never read into
+    a stored result."""
     _need_gpu(t)
     if t.dtype != torch.float32 or t.dim() != 3 or t.stride(2) != 1:
         raise RuntimeError("split_rows8: (b, r, c) fp32 views with a unit last stride only")

@@ -143,3 +143,31 @@ def test_trunk_conv2d_module_vs_fp64(ci, co, s, H):
         err = float((got.detach().double().cpu() - want.detach()).abs().max())
         sc = float(want.detach().abs().max())
         assert err <= 2e-5 * sc, (what, err, sc)
+
+
+def test_narrow_rows_the_forward_refuses_take_the_library_path():
+    """Rows too narrow for the forward's 512-pixel tile (W = 9 at stride 2 into 64 channels: 104 rows x 12 staged
+    positions against the stage's 720) are refused by avse_sconv_fwd; sconv_ok says so beforehand, and TrunkConv2d runs
+    the library convolution there (vs nn.Conv2d in fp64) instead of raising."""
+    from avse_challenge_amd.layers import TrunkConv2d
+    x = det_input((3, 64, 1, 9), 2500)
+    xg = x.to(DEV).contiguous(memory_format=CL)
+    assert not K().sconv_fwd_fits(9, 64, 2) and not K().sconv_ok(xg, 64, 2)
+    xm = torch.empty(1, device=DEV, dtype=torch.int32)
+    xq = K().split_nhwc(xg, xm)
+    with pytest.raises(RuntimeError, match="unsupported shape"):
+        K().sconv_fwd((xq, xm), tuple(x.shape), torch.zeros(64, 64, 3, 3, device=DEV), 2)
+    torch.manual_seed(8)
+    ref = torch.nn.Conv2d(64, 64, 3, stride=2, padding=1, bias=False).double()
+    ours = TrunkConv2d(64, 64, 2).to(DEV).to(memory_format=CL)
+    ours.load_state_dict({k: v.float() for k, v in ref.state_dict().items()})
+    gy = det_input((3, 64, 1, 5), 2501)
+    xr = x.double().requires_grad_(True)
+    (ref(xr) * gy.double()).sum().backward()
+    xg.requires_grad_(True)
+    y = ours(xg)
+    assert "SConv" not in type(y.grad_fn).__name__
+    (y * gy.to(DEV)).sum().backward()
+    for got, want, what in ((y, ref(xr), "y"), (xg.grad, xr.grad, "dx"), (ours.weight.grad, ref.weight.grad, "dw")):
+        err = float((got.detach().double().cpu() - want.detach()).abs().max())
+        assert err <= 2e-5 * float(want.detach().abs().max()), (what, err)

@@ -151,3 +151,13 @@ def test_time_major_tcn_chomp_matches_reference_order():
     bn2 = nn.BatchNorm1d(C).double().train()
     z = F.prelu(bn2(y.transpose(1, 2)), a)[:, :, dil:y.shape[1] - dil]   # ours: BN + PReLU, then chomp
     assert torch.allclose(z, ref, atol=1e-12)
+
+
+def test_sconv_fwd_fits_restates_the_forward_tile_limit():
+    """kernels.sconv_fwd_fits = csrc/sconv.hip's fwd_npos(TM, Wo, RS) <= NPOS_MAX (720 staged positions): the trunk
+    layers of both models fit; W = 9 at stride 2 into 64 channels needs 104 rows x 12 positions and does not."""
+    from avse_challenge_amd import kernels as K
+    for w, co, s in ((24, 64, 1), (24, 128, 2), (12, 256, 2), (6, 512, 2), (3, 512, 1), (28, 64, 1), (7, 512, 2), (7, 192, 1)):
+        assert K.sconv_fwd_fits(w, co, s), (w, co, s)
+    assert not K.sconv_fwd_fits(9, 64, 2)          # 512-pixel tile: 104 rows x 12 = 1248
+    assert K.sconv_fwd_fits(9, 128, 2)             # 256-pixel tile: 52 rows x 12 = 624
