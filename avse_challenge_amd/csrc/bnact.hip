@@ -25,6 +25,7 @@
 
 #include "bnact_cols.h"
 #include "common.h"
+#include "split16.h"
 
 namespace avse {
 namespace bnact {
@@ -77,20 +78,11 @@ __device__ inline void block_partials(const Geo& g, float (&p)[NQ][V], bool vali
     }
 }
 
-// max |out| of the workgroup -> one atomicMax on the float bits (non-negative floats order like their bits) into
-// omax: the producer-side max of the split operands (the convolution that consumes the output skips its absmax pass)
+// max |out| of the workgroup -> one atomicMax on the float bits (split16.h) into omax: the producer-side max of the
+// split operands (the convolution that consumes the output skips its absmax pass)
 __device__ inline void block_max_out(float m, uint32_t* omax) {
     __shared__ uint32_t red[THREADS / 64];
-    uint32_t b = __float_as_uint(m);
-    for (int o = 32; o >= 1; o >>= 1) b = max(b, (uint32_t)__shfl_xor((int)b, o, 64));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = b;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        b = red[0];
-#pragma unroll
-        for (int w = 1; w < THREADS / 64; ++w) b = max(b, red[w]);
-        if (b) atomicMax(omax, b);
-    }
+    block_max_publish<THREADS / 64>(m, red, omax);
 }
 
 // ---- split output ("Q": the operand layout of dconv.hip / sconv.hip, round 5)
@@ -100,23 +92,11 @@ __device__ inline void block_max_out(float m, uint32_t* omax) {
 // The split scale has to be known before the pass, so it comes from an upper bound of max |out| assembled from the
 // per-channel statistics (a bound is enough: any power-of-two scale with no fp16 overflow keeps the 22-bit split; see
 // stats_combine / bwd_combine), published as float bits where the exact max would be (y_max / dx_max).
-__device__ inline int q_split_exp(uint32_t mb) {          // dconv.hip split_exp: max 2^e in [2^14, 2^15)
-    const int ef = (int)((mb >> 23) & 0xff);
-    if (mb == 0) return 0;
-    const int k = ef == 0 ? -127 : ef - 127;
-    return min(100, max(-100, 14 - k));
-}
 // 4 channels c .. c + 3 (c % 4 == 0) of pixel r: hi at 64 (c / 16) + 2 (c % 16), lo 32 B further
 __device__ inline void q_store4(uint16_t* q, int64_t r, int64_t C, int64_t c, const float* v, float sc) {
     uint32_t hi[2], lo[2];
 #pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const float s0 = v[2 * k] * sc, s1 = v[2 * k + 1] * sc;
-        const _Float16 h0 = (_Float16)s0, h1 = (_Float16)s1;
-        const _Float16 l0 = (_Float16)(s0 - (float)h0), l1 = (_Float16)(s1 - (float)h1);
-        hi[k] = (uint32_t)__builtin_bit_cast(uint16_t, h0) | ((uint32_t)__builtin_bit_cast(uint16_t, h1) << 16);
-        lo[k] = (uint32_t)__builtin_bit_cast(uint16_t, l0) | ((uint32_t)__builtin_bit_cast(uint16_t, l1) << 16);
-    }
+    for (int k = 0; k < 2; ++k) hi[k] = split_pair(v[2 * k], v[2 * k + 1], sc, lo[k]);
     uint16_t* base = q + r * 2 * C + 32 * (c >> 4) + (c & 15);
     *reinterpret_cast<uint2*>(base) = make_uint2(hi[0], hi[1]);
     *reinterpret_cast<uint2*>(base + 16) = make_uint2(lo[0], lo[1]);
@@ -278,7 +258,7 @@ __global__ __launch_bounds__(THREADS) void apply_kernel(Geo g, const float* __re
     const int64_t j0 = ((int64_t)blockIdx.x * g.TW + tx) * V;
     float m = 0.f;
     if constexpr (QOUT) {                                 // S = 1, V = 4, no residual (host-checked)
-        const float sc = __builtin_ldexpf(1.f, q_split_exp(*ymax));
+        const float sc = split_scale(*ymax);
         if (j0 < g.CS) {
             ColConst<V, ACT> cc;
             cc.load(g, j0, stats, gamma, beta, alpha, alpha_n);
@@ -438,7 +418,7 @@ __global__ __launch_bounds__(THREADS) void bwd_apply_kernel(Geo g, const float* 
     const int64_t j0 = ((int64_t)blockIdx.x * g.TW + tx) * V;
     float m = 0.f;
     if constexpr (QOUT) {                                 // S = 1, V = 4 (host-checked)
-        const float sc = __builtin_ldexpf(1.f, q_split_exp(*dxmax));
+        const float sc = split_scale(*dxmax);
         if (j0 < g.CS)
             bwd_apply_cols<V, ACT, RES, true>(g, j0, ty, x, dy, dres, stats, gamma, beta, alpha, alpha_n, kbuf, dx, m, sc);
         return;

@@ -60,6 +60,7 @@ __global__ __launch_bounds__(THREADS) void fwd_kernel(int D, int L, const T* __r
 // dx_max (round 6): every row's max |dx| goes to the workspace after the rows' dw / db partials (wsmax[row]), and
 // rowmax_kernel folds them into *dx_max with one atomic: one same-word atomic per wave of a (b * d)-row grid cost
 // ~1.3 ms per C3 launch
+// fmaxf on floats, not split16.h's max of bits: it drops a NaN where that one publishes it, so it is not merged
 __device__ inline float wave_max(float m) {
     for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
     return m;

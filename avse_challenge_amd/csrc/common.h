@@ -79,6 +79,33 @@ __device__ inline __amdgpu_buffer_rsrc_t make_rsrc(const T* base, int64_t n_elem
     return __builtin_amdgcn_make_buffer_rsrc((void*)base, (short)0, (int)bytes, 0x00020000);
 }
 
+// ---------------------------------------------------------------- LDS-DMA (global / L2 -> LDS without VGPRs)
+typedef int i4_t __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) void lds_void_t;
+
+// Wave-uniform buffer resource words over [base, base + bytes), bytes >= 0: reads past it return 0.  For dma16's inline
+// asm only; the compiler's buffer builtins (bufld / bufst) take make_rsrc's __amdgpu_buffer_rsrc_t above.
+__device__ inline i4_t dma_rsrc(const void* base, int64_t bytes) {
+    if (bytes > 0x7FFFFFF0LL) bytes = 0x7FFFFFF0LL;
+    const uint64_t a = (uint64_t)base;
+    return i4_t{__builtin_amdgcn_readfirstlane((int)(uint32_t)a), __builtin_amdgcn_readfirstlane((int)((a >> 32) & 0xffff)),
+                __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000};
+}
+
+// One 16-B-per-lane LDS-DMA wave-instruction: LDS[lds_addr + 16 lane] = buffer[voff] (0 past the range).  Inline asm on
+// purpose: the compiler tracks its own LDS-DMA builtin as a pending write to the whole staging array and then waits
+// vmcnt(0) before every ds_read of it, which drains the stages in flight; the callers count their vmcnt waits by hand.
+// A kernel that calls this must use M0 for nothing else.
+__device__ inline void dma16(i4_t r, uint32_t lds_addr, uint32_t voff) {
+    asm volatile("s_mov_b32 m0, %2\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds" ::"v"(voff), "s"(r), "s"(lds_addr)
+                 : "memory");
+}
+
+// the wave-uniform LDS byte address of p
+__device__ inline uint32_t lds_u32(const void* p) {
+    return __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(const lds_void_t*)p);
+}
+
 __device__ inline float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 
 // packed fp32 pair: v_pk_mul_f32 / v_pk_fma_f32 / v_pk_add_f32 do two lanes' worth of f32 math per

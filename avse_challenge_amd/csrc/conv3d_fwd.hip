@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "split16.h"
 
 namespace avse {
 namespace c3f {
@@ -53,19 +54,13 @@ constexpr int XM_GRID = 512;                     // blocks of the x absmax pass 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 
-// max |v| over n floats -> *mb (float bits) by one 1024-thread block (the weights; the x pass's partial maxima)
+// max |v| over n floats -> *mb (float bits) by one 1024-thread block, 16 waves (the weights; the x pass's partial maxima)
 __global__ void wmax16_kernel(const float* __restrict__ w, int n, uint32_t* __restrict__ mb) {
     float m = 0.f;
     for (int i = threadIdx.x; i < n; i += blockDim.x) m = fmaxf(m, fabsf(w[i]));
-    uint32_t b = __float_as_uint(m);
-    for (int o = 32; o >= 1; o >>= 1) b = max(b, (uint32_t)__shfl_xor((int)b, o, 64));
     __shared__ uint32_t red[16];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = b;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < (int)(blockDim.x >> 6); ++k) b = max(b, red[k]);
-        *mb = b;
-    }
+    const uint32_t b = block_max_bits<16>(m, red);
+    if (threadIdx.x == 0) *mb = b;                  // a plain store: a zero maximum is published too
 }
 
 // partial max |x| per block over a grid-stride walk (float4 when x is 16-B aligned, 2 loads in flight per thread)
@@ -91,48 +86,20 @@ __global__ __launch_bounds__(256) void xmax_kernel(const float* __restrict__ x, 
     } else {
         for (int64_t j = i0; j < n; j += stride) m0 = fmaxf(m0, fabsf(x[j]));
     }
-    uint32_t b = __float_as_uint(fmaxf(m0, m1));
-    for (int o = 32; o >= 1; o >>= 1) b = max(b, (uint32_t)__shfl_xor((int)b, o, 64));
     __shared__ uint32_t red[4];
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = b;
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = __uint_as_float(max(max(red[0], red[1]), max(red[2], red[3])));
-}
-
-typedef int i4_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void_t;
-
-__device__ inline i4_t rsrc16(const void* base, int64_t bytes) {
-    if (bytes > 0x7FFFFFF0LL) bytes = 0x7FFFFFF0LL;
-    const uint64_t a = (uint64_t)base;
-    return i4_t{__builtin_amdgcn_readfirstlane((int)(uint32_t)a), __builtin_amdgcn_readfirstlane((int)((a >> 32) & 0xffff)),
-                __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000};
-}
-// one 16-B-per-lane LDS-DMA wave-instruction (inline asm: the builtin makes the compiler wait vmcnt(0) before every
-// ds_read of the array).  Nothing else in this kernel uses M0.
-__device__ inline void dma16(i4_t r, uint32_t lds_addr, uint32_t voff) {
-    asm volatile("s_mov_b32 m0, %2\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds" ::"v"(voff), "s"(r), "s"(lds_addr)
-                 : "memory");
-}
-
-__device__ inline int split_exp16(uint32_t mb) {
-    const int ef = (int)((mb >> 23) & 0xff);
-    if (mb == 0) return 0;
-    const int k = ef == 0 ? -127 : ef - 127;
-    return min(100, max(-100, 14 - k));
+    const uint32_t b = block_max_bits<4>(fmaxf(m0, m1), red);
+    if (threadIdx.x == 0) part[blockIdx.x] = __uint_as_float(b);
 }
 
 __global__ void wprep16_kernel(const float* __restrict__ w, int npl, const uint32_t* __restrict__ mb,
                                uint16_t* __restrict__ wq) {
     const int n = npl * F16_KSTEPS * COUT * 16;
-    const float sc = __builtin_ldexpf(1.f, split_exp16(*mb));
+    const float sc = split_scale(*mb);
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const int k = i % 16, co = (i / 16) % COUT, st = (i / (16 * COUT)) % F16_KSTEPS, pl = i / (16 * COUT * F16_KSTEPS);
         const int kh = 2 * st + k / 8, kw = k % 8;
         const float v = (kh < KH && kw < KW) ? w[(((int64_t)co * npl + pl) * KH + kh) * KW + kw] * sc : 0.f;
-        const _Float16 hi = (_Float16)v, lo = (_Float16)(v - (float)hi);
-        wq[i] = __builtin_bit_cast(uint16_t, hi);
-        wq[n + i] = __builtin_bit_cast(uint16_t, lo);
+        split16(v, wq[i], wq[n + i]);
     }
 }
 
@@ -171,7 +138,7 @@ __global__ __launch_bounds__(THREADS, 2) void fwd16_kernel(int B, int TT, const 
     const int64_t nx = (int64_t)B * CIN * TT * H * W;     // < 2^31 bytes (checked at launch)
     const auto rx = make_rsrc(x, nx);
     const int OOB = (int)nx;
-    const float xsc = XS ? __builtin_ldexpf(1.f, split_exp16(mb[1])) : 1.f;
+    const float xsc = XS ? split_scale(mb[1]) : 1.f;
 
     // B-operand byte offsets (without the k-step row) per pixel tile: copy (wo & 1), row 2 (ho - r0), the word of
     // column 2 wo - 3
@@ -185,8 +152,8 @@ __global__ __launch_bounds__(THREADS, 2) void fwd16_kernel(int B, int TT, const 
         boff[j] = ((cp * G16::IRS + 2 * (ho - r0)) * G16::RC + (2 * wo - 2 * cp)) * 2;
     }
     float xr[G16::XPT];
-    const i4_t rwq = rsrc16(wq, (int64_t)2 * G::NPL * WB_HALF);
-    const uint32_t lds0 = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(const lds_void_t*)lds);
+    const i4_t rwq = dma_rsrc(wq, (int64_t)2 * G::NPL * WB_HALF);
+    const uint32_t lds0 = lds_u32(lds);
     // x of plane pl into registers; its weights (hi 8 KB, lo 8 KB) by LDS-DMA straight into buffer buf (free: its
     // last readers passed the barrier before this call)
     auto prefetch = [&](int pl, int buf) {
@@ -217,10 +184,10 @@ __global__ __launch_bounds__(THREADS, 2) void fwd16_kernel(int B, int TT, const 
             if (e < G::IR * G::IC) {
                 const int c = e % G::IC, row = e / G::IC;
                 const float v = xr[i] * xsc;                                    // uint8: exact, xsc = 1
-                const _Float16 h = (_Float16)v;
+                const _Float16 h = (_Float16)v;                                 // split16 written out: the lo half is
                 xs[row * G16::RC + c] = h;                                      // copy 0: column c - 3 at c
                 if (c >= 2) xs[(G16::IRS + row) * G16::RC + c - 2] = h;         // copy 1: column c - 3 at c - 2
-                if constexpr (XS) {
+                if constexpr (XS) {                                             // formed after the hi stores (schedule)
                     const _Float16 l = (_Float16)(v - (float)h);
                     xl[row * G16::RC + c] = l;
                     if (c >= 2) xl[(G16::IRS + row) * G16::RC + c - 2] = l;
@@ -294,8 +261,8 @@ __global__ __launch_bounds__(THREADS, 2) void fwd16_kernel(int B, int TT, const 
         }
     }
     // two factors: 2^-(e + f) alone can leave the fp32 range where the product does not
-    const float unscale = __builtin_ldexpf(1.f, -split_exp16(mb[0]));
-    const float unscale_x = XS ? __builtin_ldexpf(1.f, -split_exp16(mb[1])) : 1.f;
+    const float unscale = __builtin_ldexpf(1.f, -split_exp(mb[0]));
+    const float unscale_x = XS ? __builtin_ldexpf(1.f, -split_exp(mb[1])) : 1.f;
     float* yb = y + ((int64_t)b * COUT * TT + t) * G::PLANE_PX;
 #pragma unroll
     for (int j = 0; j < TILES_PER_WAVE; ++j) {
@@ -314,8 +281,12 @@ __global__ __launch_bounds__(THREADS, 2) void fwd16_kernel(int B, int TT, const 
 
 // workspace: wq (2 NPL WB_HALF bytes) | mb[0] = max |W|, mb[1] = max |x| (16 B) | the x pass's partial maxima
 template <int CIN, int H, int W>
+constexpr int64_t mb_offset() {                 // byte offset of mb[0]: the one statement of where the max words sit
+    return 2 * (int64_t)Geo<CIN, H, W>::NPL * WB_HALF;
+}
+template <int CIN, int H, int W>
 constexpr int64_t ws_bytes() {
-    return 2 * (int64_t)Geo<CIN, H, W>::NPL * WB_HALF + 16 + 4 * XM_GRID;
+    return mb_offset<CIN, H, W>() + 16 + 4 * XM_GRID;
 }
 
 template <typename T, int CIN, int H, int W>
@@ -324,7 +295,7 @@ int launch(int64_t B, int64_t TT, const void* x, const float* w, float* y, float
     if ((int64_t)B * CIN * TT * H * W >= (1LL << 31) / (int64_t)sizeof(T)) return AVSE_ESHAPE;   // 32-bit offsets
     if (B * TT * G::NT >= (1LL << 31)) return AVSE_ESHAPE;
     uint16_t* wq = reinterpret_cast<uint16_t*>(workspace);
-    uint32_t* mb = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(workspace) + 2 * G::NPL * WB_HALF);
+    uint32_t* mb = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(workspace) + mb_offset<CIN, H, W>());
     float* part = reinterpret_cast<float*>(mb + 4);
     hipLaunchKernelGGL(wmax16_kernel, dim3(1), dim3(1024), 0, st, w, G::NPL * COUT * KH * KW, mb);
     AVSE_CHECK_LAUNCH();
@@ -359,6 +330,13 @@ extern "C" {
 int64_t avse_conv3d_fwd_workspace_bytes(int64_t CIN, int64_t H, int64_t W) {
     if (CIN == 3 && H == 96 && W == 96) return ws_bytes<3, 96, 96>();
     if (CIN == 1 && H == 112 && W == 112) return ws_bytes<1, 112, 112>();
+    return 0;
+}
+
+// byte offset of mb[1] (max |x| bits of an fp32 forward) inside the workspace; <= 0: shape not compiled in
+int64_t avse_conv3d_fwd_xmax_offset(int64_t CIN, int64_t H, int64_t W) {
+    if (CIN == 3 && H == 96 && W == 96) return mb_offset<3, 96, 96>() + 4;
+    if (CIN == 1 && H == 112 && W == 112) return mb_offset<1, 112, 112>() + 4;
     return 0;
 }
 

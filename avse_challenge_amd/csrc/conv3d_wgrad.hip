@@ -19,6 +19,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "split16.h"
 
 namespace avse {
 namespace c3w {
@@ -176,13 +177,6 @@ constexpr int YS16 = MAX_WO + 8;                    // fp16 per dY row (hi, lo p
 constexpr int RING = 8;                             // staged rows per input plane
 constexpr int RUN = 16;                             // output rows per run (at most)
 
-__device__ inline int split_exp_w(uint32_t mb) {
-    const int ef = (int)((mb >> 23) & 0xff);
-    if (mb == 0) return 0;
-    const int k = ef == 0 ? -127 : ef - 127;
-    return min(100, max(-100, 14 - k));
-}
-
 // runs: s.rows = B * TO * nrun units (b, t, run), run r covering output rows r * s.hc .. min(HO, (r + 1) * s.hc) - 1
 template <typename XT, int NTW, int RPW>
 __global__ __launch_bounds__(THREADS, 2) void wgrad16_kernel(Shape s, const XT* __restrict__ x,
@@ -247,8 +241,8 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad16_kernel(Shape s, const XT* 
     const int ny = (int)((int64_t)s.B * COUT * s.TO * yplane);
     const auto rx = make_rsrc(x, nx);
     const auto ry = make_rsrc(dy, ny);
-    const float sc = __builtin_ldexpf(1.f, split_exp_w(*dymax));
-    const float xsc = XS ? __builtin_ldexpf(1.f, split_exp_w(*xmax)) : 1.f;
+    const float sc = split_scale(*dymax);
+    const float xsc = XS ? split_scale(*xmax) : 1.f;
     float xr[RPW][2], yr[16];
     const int wo16 = ks * 16;
     const int nrun = (s.HO + s.hc - 1) / s.hc;
@@ -325,7 +319,7 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad16_kernel(Shape s, const XT* 
                         if (c < 2 * PARW) {
                             // beyond the window: zeros (the zero-weight 8th tap reads up to 2 columns past it)
                             const float f = c < WIN ? xr[i][qq] * xsc : 0.f;          // uint8: exact, xsc = 1
-                            const _Float16 hv = (_Float16)f;
+                            const _Float16 hv = (_Float16)f;          // split16 written out: lo after the hi stores
                             const int p = c & 1, mm = c >> 1;
                             xs[rr * XROW + (2 * p) * PARW + mm] = hv;                     // copy 0
                             if (mm >= 1) xs[rr * XROW + (2 * p + 1) * PARW + mm - 1] = hv; // copy 1: one element later
@@ -343,9 +337,7 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad16_kernel(Shape s, const XT* 
         for (int i = 0; i < 16; ++i) {
             if (lane < wo16) {
                 const float v = (lane < s.WO ? yr[i] : 0.f) * sc;
-                const _Float16 h = (_Float16)v;
-                yh[(wave + 4 * i) * YS16 + lane] = h;
-                yl[(wave + 4 * i) * YS16 + lane] = (_Float16)(v - (float)h);
+                split16(v, yh[(wave + 4 * i) * YS16 + lane], yl[(wave + 4 * i) * YS16 + lane]);
             }
         }
         __syncthreads();
@@ -388,8 +380,8 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad16_kernel(Shape s, const XT* 
             }
         }
     }
-    const float unscale = __builtin_ldexpf(1.f, -split_exp_w(*dymax));
-    const float unscale_x = XS ? __builtin_ldexpf(1.f, -split_exp_w(*xmax)) : 1.f;
+    const float unscale = __builtin_ldexpf(1.f, -split_exp(*dymax));
+    const float unscale_x = XS ? __builtin_ldexpf(1.f, -split_exp(*xmax)) : 1.f;
     float* pp = part + (int64_t)blockIdx.x * COUT * s.N;
 #pragma unroll
     for (int m = 0; m < 2; ++m)

@@ -35,14 +35,13 @@
 
 #include "bnact_cols.h"
 #include "common.h"
+#include "split16.h"
 
 namespace avse {
 namespace dcf {
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef int i4_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void_t;
 
 constexpr int C = 64, KS = 5, NQ = 4, TP = 256, THREADS = 256, WAVES = THREADS / 64;
 constexpr int ROWB = 64;                       // LDS bytes per staged row (position or W row): hi 16 | lo 16 channels
@@ -56,32 +55,6 @@ constexpr int MAXP = (XIMG_MAX + WIMG) / 1024 / WAVES + 1;   // LDS-DMA pieces p
 static_assert(NBUF * STAGE <= 160 * 1024, "LDS");
 
 __device__ inline int swz(int r) { return (r >> 2) & 3; }
-
-// power-of-two scale exponent e for a tensor whose max |x| has the float bits mb: max 2^e in [2^14, 2^15)
-__device__ inline int split_exp(uint32_t mb) {
-    const int ef = (int)((mb >> 23) & 0xff);
-    if (mb == 0) return 0;
-    const int k = ef == 0 ? -127 : ef - 127;
-    return min(100, max(-100, 14 - k));
-}
-
-__device__ inline i4_t rsrc_of(const void* base, int64_t bytes) {
-    if (bytes > 0x7FFFFFF0LL) bytes = 0x7FFFFFF0LL;
-    const uint64_t a = (uint64_t)base;
-    return i4_t{__builtin_amdgcn_readfirstlane((int)(uint32_t)a), __builtin_amdgcn_readfirstlane((int)((a >> 32) & 0xffff)),
-                __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000};
-}
-
-// one 16-B-per-lane LDS-DMA wave-instruction: LDS[lds_addr + 16 lane] = buffer[voff] (0 past the range).  Inline asm:
-// the compiler's LDS-DMA builtin makes it wait vmcnt(0) before every ds_read of the array.  Nothing else uses M0.
-__device__ inline void dma16(i4_t r, uint32_t lds_addr, uint32_t voff) {
-    asm volatile("s_mov_b32 m0, %2\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds" ::"v"(voff), "s"(r), "s"(lds_addr)
-                 : "memory");
-}
-
-__device__ inline uint32_t lds_u32(const void* p) {
-    return __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(const lds_void_t*)p);
-}
 
 // s_waitcnt vmcnt(n) for a wave-uniform n in 0 .. 12 (the immediate must be a constant)
 __device__ inline void wait_all_but(int n) {
@@ -143,8 +116,8 @@ __global__ __launch_bounds__(64 * NW, WGS) void fwd_kernel(Args a) {
     // pixels of the tile in its first, second and third row, and the segments' first positions
     const int n0 = min(TPX, a.W - w0), n1 = min(TPX - n0, a.W), n2 = TPX - n0 - n1;
     const int S1 = n0 + 4 * D, S2 = n0 + n1 + 8 * D;
-    const i4_t rx = rsrc_of(a.xq, (int64_t)a.N * HW * 256);
-    const i4_t rw = rsrc_of(a.wq, (int64_t)NSTG * WIMG);
+    const i4_t rx = dma_rsrc(a.xq, (int64_t)a.N * HW * 256);
+    const i4_t rw = dma_rsrc(a.wq, (int64_t)NSTG * WIMG);
     const uint32_t lds0 = lds_u32(lds);
 
     // this wave's LDS-DMA pieces of a stage: k = wave + NW m; X pieces (k < PX) carry the lane's position column (or -1
@@ -382,8 +355,8 @@ __global__ __launch_bounds__(WTHREADS, 1) void wgrad_kernel(WArgs a) {
     const int r = bid / KS, kh = bid % KS;
     const int c_lo = (int)((int64_t)r * a.chunks / a.ranges), c_hi = (int)((int64_t)(r + 1) * a.chunks / a.ranges);
     const int HW = a.H * a.W;
-    const i4_t rx = rsrc_of(a.xq, (int64_t)a.N * HW * PIXB);
-    const i4_t ry = rsrc_of(a.dyq, (int64_t)a.N * HW * PIXB);
+    const i4_t rx = dma_rsrc(a.xq, (int64_t)a.N * HW * PIXB);
+    const i4_t ry = dma_rsrc(a.dyq, (int64_t)a.N * HW * PIXB);
     const uint32_t lds0 = lds_u32(lds);
     const int npieces = (PT - wave + WWAVES - 1) / WWAVES;
     const int pr = lane >> 4, pc = lane & 15;                    // a piece's lane: row (of 4), physical chunk
@@ -533,9 +506,8 @@ __global__ void wgrad_reduce_kernel(const float* __restrict__ part, const float*
 inline int wgrad_ranges(int chunks) { return std::max(1, std::min(chunks, 256 / KS * 1)); }
 
 // ------------------------------------------------------------------------------------------------ operand preparation
-// max |x| over n floats -> atomicMax on the float bits (non-negative floats order like their bits; NaN wins).  One
-// atomic per 1024-thread workgroup of a 256-workgroup grid: the word's atomics serialise at the memory side (~17 ns
-// each), so one per wave of a 2048 x 256 grid cost ~140 us of a 165 us pass (profiles/r05v3_avse1_timed_window_stats.csv)
+// max |x| over n floats -> atomicMax on the float bits (split16.h), one per 1024-thread workgroup of a 256-workgroup
+// grid: one per wave of a 2048 x 256 grid cost ~140 us of a 165 us pass (profiles/r05v3_avse1_timed_window_stats.csv)
 constexpr int AMAX_NT = 1024, AMAX_GRID = 256;
 __global__ __launch_bounds__(AMAX_NT) void absmax_kernel(const float4* x, int64_t n4, uint32_t* out) {
     __shared__ uint32_t red[AMAX_NT / 64];
@@ -548,35 +520,20 @@ __global__ __launch_bounds__(AMAX_NT) void absmax_kernel(const float4* x, int64_
 #pragma unroll
         for (int u = 0; u < 4; ++u) m = fmaxf(m, fmaxf(fmaxf(fabsf(v[u].x), fabsf(v[u].y)), fmaxf(fabsf(v[u].z), fabsf(v[u].w))));
     }
-    uint32_t b = __float_as_uint(m);
-    for (int o = 32; o >= 1; o >>= 1) b = max(b, (uint32_t)__shfl_xor((int)b, o, 64));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = b;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 0; k < AMAX_NT / 64; ++k) b = max(b, red[k]);
-        if (b) atomicMax(out, b);
-    }
-}
-
-__device__ inline uint32_t split2(float x0, float x1, float sc, uint32_t& lo) {
-    const float s0 = x0 * sc, s1 = x1 * sc;
-    const _Float16 h0 = (_Float16)s0, h1 = (_Float16)s1;
-    const _Float16 l0 = (_Float16)(s0 - (float)h0), l1 = (_Float16)(s1 - (float)h1);
-    lo = (uint32_t)__builtin_bit_cast(uint16_t, l0) | ((uint32_t)__builtin_bit_cast(uint16_t, l1) << 16);
-    return (uint32_t)__builtin_bit_cast(uint16_t, h0) | ((uint32_t)__builtin_bit_cast(uint16_t, h1) << 16);
+    block_max_publish<AMAX_NT / 64>(m, red, out);
 }
 
 // NHWC fp32 (n_pix x 64) -> Q4 (n_pix x 4 quarters x [hi 16 | lo 16] fp16); thread = one (pixel, quarter)
 __global__ void split_kernel(const float* x, int64_t nq, const uint32_t* maxbits, uint4* xq) {
-    const float sc = __builtin_ldexpf(1.f, split_exp(maxbits[0]));
+    const float sc = split_scale(maxbits[0]);
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < nq; i += (int64_t)gridDim.x * blockDim.x) {
         const float4* s = reinterpret_cast<const float4*>(x + i * 16);
         uint32_t hi[8], lo[8];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const float4 v = s[k];
-            hi[2 * k] = split2(v.x, v.y, sc, lo[2 * k]);
-            hi[2 * k + 1] = split2(v.z, v.w, sc, lo[2 * k + 1]);
+            hi[2 * k] = split_pair(v.x, v.y, sc, lo[2 * k]);
+            hi[2 * k + 1] = split_pair(v.z, v.w, sc, lo[2 * k + 1]);
         }
         uint4* d = xq + i * 4;
         d[0] = uint4{hi[0], hi[1], hi[2], hi[3]};
@@ -593,25 +550,17 @@ __global__ __launch_bounds__(1024) void wprep_kernel(const float* w, int transpo
     constexpr int TOT = C * C * KS * KS;
     float m = 0.f;
     for (int i = threadIdx.x; i < TOT; i += blockDim.x) m = fmaxf(m, fabsf(w[i]));
-    uint32_t b = __float_as_uint(m);
-    for (int o = 32; o >= 1; o >>= 1) b = max(b, (uint32_t)__shfl_xor((int)b, o, 64));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = b;
-    __syncthreads();
-    b = 0;
-    for (int k = 0; k < (int)(blockDim.x >> 6); ++k) b = max(b, red[k]);
-    if (threadIdx.x == 0) maxbits[1] = b;
-    const float sc = __builtin_ldexpf(1.f, split_exp(b));
+    const uint32_t b = block_max_bits<16, true>(m, red);        // the launch is 1024 threads
+    if (threadIdx.x == 0) maxbits[1] = b;                       // a plain store: a zero maximum is published too
+    const float sc = split_scale(b);
     // destination element e: stage s = kh * 4 + q, kw, o, plane, c (16)
     for (int e = threadIdx.x; e < TOT; e += blockDim.x) {
         const int c = e % 16, o = (e / 16) % C, kw = (e / (16 * C)) % KS, s = e / (16 * C * KS);
         const int kh = s / NQ, q = s % NQ, i = q * 16 + c;
         const float v = transposed ? w[((i * C + o) * KS + (KS - 1 - kh)) * KS + (KS - 1 - kw)]
                                    : w[((o * C + i) * KS + kh) * KS + kw];
-        const float sv = v * sc;
-        const _Float16 h = (_Float16)sv, l = (_Float16)(sv - (float)h);
         const int64_t row = ((int64_t)s * KS + kw) * C + o;
-        wq[row * 32 + c] = __builtin_bit_cast(uint16_t, h);
-        wq[row * 32 + 16 + c] = __builtin_bit_cast(uint16_t, l);
+        split16(v * sc, wq[row * 32 + c], wq[row * 32 + 16 + c]);
     }
 }
 
@@ -625,17 +574,12 @@ __global__ __launch_bounds__(1024) void wprep2_kernel(const float* w, uint32_t* 
     constexpr int TOT = C * C * KS * KS, PER = KS * C * 16;       // elements per stage
     float m = 0.f;
     for (int i = threadIdx.x; i < TOT; i += 1024) m = fmaxf(m, fabsf(w[i]));
-    uint32_t b = __float_as_uint(m);
-    for (int o = 32; o >= 1; o >>= 1) b = max(b, (uint32_t)__shfl_xor((int)b, o, 64));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = b;
-    __syncthreads();
-    b = 0;
-    for (int k = 0; k < 16; ++k) b = max(b, red[k]);
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
+    const uint32_t b = block_max_bits<16, true>(m, red);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {                  // plain stores: a zero maximum is published too
         mb0[1] = b;
         if (mb1) mb1[1] = b;
     }
-    const float sc = __builtin_ldexpf(1.f, split_exp(b));
+    const float sc = split_scale(b);
     const int transposed = blockIdx.x / NSTG, s = blockIdx.x % NSTG;
     uint16_t* wq = transposed ? wq1 : wq0;
     const int kh = s / NQ, q = s % NQ;
@@ -644,11 +588,8 @@ __global__ __launch_bounds__(1024) void wprep2_kernel(const float* w, uint32_t* 
         const int i = q * 16 + c;
         const float v = transposed ? w[((i * C + o) * KS + (KS - 1 - kh)) * KS + (KS - 1 - kw)]
                                    : w[((o * C + i) * KS + kh) * KS + kw];
-        const float sv = v * sc;
-        const _Float16 h = (_Float16)sv, l = (_Float16)(sv - (float)h);
         const int64_t row = ((int64_t)s * KS + kw) * C + o;
-        wq[row * 32 + c] = __builtin_bit_cast(uint16_t, h);
-        wq[row * 32 + 16 + c] = __builtin_bit_cast(uint16_t, l);
+        split16(v * sc, wq[row * 32 + c], wq[row * 32 + 16 + c]);
     }
 }
 

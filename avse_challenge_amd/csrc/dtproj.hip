@@ -25,6 +25,7 @@
 // Isolated (tools/dtproj_bench.py, profiles/r05v_dtproj_ab.jsonl): C5 bf16 0.18 ms (the VALU version 0.28, the
 // earlier MFMA versions with one workgroup per (64 channels, 256 steps) 0.31-0.34), C3 fp32 0.43 (VALU 0.41).
 #include "common.h"
+#include "split16.h"
 
 namespace avse {
 namespace dtp {
@@ -50,14 +51,6 @@ struct Args {
     int softplus;
 };
 
-// same function as dconv.hip: max |v| 2^e in [2^14, 2^15)
-__device__ inline int split_exp(uint32_t mb) {
-    const int ef = (int)((mb >> 23) & 0xff);
-    if (mb == 0) return 0;
-    const int k = ef == 0 ? -127 : ef - 127;
-    return min(100, max(-100, 14 - k));
-}
-
 template <typename T> struct ld4;
 template <> struct ld4<float> {
     __device__ static inline float4 ld(__amdgpu_buffer_rsrc_t r, int e) {
@@ -72,8 +65,6 @@ template <> struct ld4<bf16_t> {
                            __uint_as_float(v[1] << 16), __uint_as_float(v[1] & 0xffff0000u));
     }
 };
-
-__device__ inline uint16_t h16(float v) { return __builtin_bit_cast(uint16_t, (_Float16)v); }
 
 // x image: k-row r (512 B = 256 steps of 16 bits), step t at r 512 + 16 ((t >> 3) ^ ((r & 3) << 2)) + 2 (t & 7)
 __device__ inline int ximg_off(int r, int t) { return r * 512 + 16 * ((t >> 3) ^ ((r & 3) << 2)) + 2 * (t & 7); }
@@ -154,6 +145,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4))) vo
     float sx = 1.f;
     int ex = 0;
     if constexpr (F32) {
+        // the workgroup maximum written out: through split16.h's helpers this kernel's instruction schedule changed
         uint32_t bx = __float_as_uint(mx);
         for (int o = 32; o >= 1; o >>= 1) bx = max(bx, (uint32_t)__shfl_xor((int)bx, o, 64));
         if (lane == 0) red[wave] = bx;
@@ -170,10 +162,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4))) vo
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             if constexpr (F32) {
-                const float sv = v[e] * sx;
-                const _Float16 hh = (_Float16)sv;
-                h[e] = __builtin_bit_cast(uint16_t, hh);
-                l[e] = h16(sv - (float)hh);
+                split16(v[e] * sx, h[e], l[e]);
             } else {
                 h[e] = (uint16_t)(__float_as_uint(v[e]) >> 16);        // the bf16 value as loaded
             }
@@ -216,19 +205,17 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4))) vo
             for (int s = 0; s < NKS; ++s)
 #pragma unroll
                 for (int e = 0; e < 8; ++e) mw = fmaxf(mw, fabsf(wn[s][e]));
-            uint32_t bw = __float_as_uint(mw);
-            for (int o = 32; o >= 1; o >>= 1) bw = max(bw, (uint32_t)__shfl_xor((int)bw, o, 64));
-            const int ew = split_exp(bw);
+            const int ew = split_exp(wave_max_bits(__float_as_uint(mw)));
             const float sw = __builtin_ldexpf(1.f, ew);
             unscale = __builtin_ldexpf(1.f, -(ex + ew));
 #pragma unroll
             for (int s = 0; s < NKS; ++s)
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
-                    const float sv = wn[s][e] * sw;
-                    const _Float16 hh = (_Float16)sv;
+                    _Float16 hh, ll;
+                    split16(wn[s][e] * sw, hh, ll);
                     wh[s][e] = hh;
-                    wl[s][e] = (_Float16)(sv - (float)hh);
+                    wl[s][e] = ll;
                 }
         } else {
 #pragma unroll

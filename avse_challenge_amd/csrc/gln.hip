@@ -12,6 +12,7 @@
 // shifted by the sample's first element, which removes the E[x^2]-E[x]^2 cancellation.
 // HBM: fwd = 2 reads + 1 write of x, bwd = 2 reads of (x, dy) + 1 write of dx.
 #include "common.h"
+#include "split16.h"
 
 namespace avse {
 namespace gln {
@@ -129,15 +130,6 @@ __device__ inline float2 sample_stats(double2 sums, int C, int K, float shift, f
 // 0.0965 -> 0.101 ms).
 __device__ inline int second_pass_row() { return gridDim.x - 1 - blockIdx.x; }
 
-// power-of-two scale of the split planes from the bits of an upper bound of max |y| (the projection GEMM's split_exp:
-// bound 2^e in [2^14, 2^15); values up to twice the bound still fit fp16)
-__device__ inline int split_exp_gln(uint32_t mb) {
-    const int ef = (int)((mb >> 23) & 0xff);
-    if (mb == 0) return 0;
-    const int k = ef == 0 ? -127 : ef - 127;
-    return min(100, max(-100, 14 - k));
-}
-
 // Q output: the apply's y as the split-fp16 planes of the 1x1 Conv1d GEMM that consumes it (csrc/projgemm.hip
 // avse_gemm_f32s): hi = fp16(y 2^e), lo = fp16(y 2^e - hi) in rows of kp (a multiple of 8) elements; the padding
 // columns K .. kp - 1 are written as 0 (a weight-gradient GEMM over time chunks sums over them)
@@ -155,10 +147,7 @@ __device__ inline void q_store_quad(const QOut& q, int row, int t, int K, const 
     for (int e2 = 0; e2 < 2; ++e2) {
         const float s0 = t + 2 * e2 < K ? o4[2 * e2] * sc : 0.f;
         const float s1 = t + 2 * e2 + 1 < K ? o4[2 * e2 + 1] * sc : 0.f;
-        const _Float16 h0 = (_Float16)s0, h1 = (_Float16)s1;
-        const _Float16 l0 = (_Float16)(s0 - (float)h0), l1 = (_Float16)(s1 - (float)h1);
-        h[e2] = (uint32_t)__builtin_bit_cast(uint16_t, h0) | ((uint32_t)__builtin_bit_cast(uint16_t, h1) << 16);
-        l[e2] = (uint32_t)__builtin_bit_cast(uint16_t, l0) | ((uint32_t)__builtin_bit_cast(uint16_t, l1) << 16);
+        h[e2] = split_pair(s0, s1, l[e2]);
     }
     const int64_t off = (int64_t)row * q.kp + t;
     *reinterpret_cast<uint2*>(q.hi + off) = uint2{h[0], h[1]};
@@ -194,7 +183,7 @@ __global__ __launch_bounds__(THREADS) void apply_fused_kernel(int row0, int C, i
     float* yr = QO ? nullptr : y + (int64_t)row * K;
     const auto rx = make_rsrc(xr, K), ry = make_rsrc(QO ? xr : yr, K);
     float sc = 1.f;
-    if constexpr (QO) sc = __builtin_ldexpf(1.f, split_exp_gln(*q.maxbits));
+    if constexpr (QO) sc = split_scale(*q.maxbits);
     for (int t0 = 0; t0 < K; t0 += UB4 * V4 * THREADS) {
         float4 xv[UB4];
 #pragma unroll
@@ -234,6 +223,7 @@ __global__ __launch_bounds__(256) void q_bound_kernel(int C, int K, const float*
         const float2 e = mm[(int64_t)b * C + c];
         m = fmaxf(m, fmaxf(fabsf(g * e.x + o), fabsf(g * e.y + o)));
     }
+    // fmaxf on floats, not split16.h's max of bits: it drops a NaN where that one publishes it, so it is not merged
     for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
     if ((threadIdx.x & 63) == 0) fred[threadIdx.x >> 6] = m;
     __syncthreads();
@@ -316,6 +306,7 @@ __global__ __launch_bounds__(256) void q_bwd_bound_kernel(int C, int K, const fl
         const float2 e = mm[(int64_t)b * C + c];
         m = fmaxf(m, sl * (fabsf(gamma[c]) * e.x + smx + e.y * smy));
     }
+    // fmaxf on floats, not split16.h's max of bits: it drops a NaN where that one publishes it, so it is not merged
     for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
     if ((threadIdx.x & 63) == 0) fred[threadIdx.x >> 6] = m;
     __syncthreads();
@@ -393,7 +384,7 @@ __global__ __launch_bounds__(THREADS) void bwd_apply_kernel(int row0, int C, int
     float* dr = QO ? nullptr : dx + (int64_t)row * K;
     const auto rx = make_rsrc(xr, K), rg = make_rsrc(gr, K), rd = make_rsrc(QO ? gr : dr, K);
     float sc = 1.f;
-    if constexpr (QO) sc = __builtin_ldexpf(1.f, split_exp_gln(*q.maxbits));
+    if constexpr (QO) sc = split_scale(*q.maxbits);
     float da = 0.f;
     for (int t0 = 0; t0 < K; t0 += UB4 * V4 * THREADS) {
         float4 xv[UB4], gv[UB4];

@@ -33,6 +33,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "split16.h"
 
 namespace avse {
 namespace pg {
@@ -41,7 +42,6 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s4_t __attribute__((ext_vector_type(4)));
 typedef short s8_t __attribute__((ext_vector_type(8)));
 typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __attribute__((address_space(3))) s4_t lds_s4_t;
 
 constexpr int BT = 256, THREADS = 512, WAVES = THREADS / 64;
@@ -79,7 +79,7 @@ struct Args {
     int32_t c_vec16;                       // bf16 out: rows 16-B aligned (c and c_sq * 2 multiples of 16)
     float alpha;
     // split mode (fp32 GEMM on fp16 hi / lo planes): the lo planes (same strides as p / q) and the device max-|x| bits
-    // the planes were scaled by (dconv.hip split_exp)
+    // the planes were scaled by (split16.h split_exp)
     const uint16_t* p_lo;
     const uint16_t* q_lo;
     const uint32_t* p_max;
@@ -94,37 +94,9 @@ __device__ inline int64_t batch_off(int b, int nsub, int64_t bs, int64_t bs2) {
     return nsub > 1 ? (int64_t)(b / nsub) * bs + (int64_t)(b % nsub) * bs2 : (int64_t)b * bs;
 }
 
-// power-of-two split scale of a tensor with max |x| bits mb (the same function as dconv.hip's / gemmsplit's)
-__device__ inline int split_exp_pg(uint32_t mb) {
-    const int ef = (int)((mb >> 23) & 0xff);
-    if (mb == 0) return 0;
-    const int k = ef == 0 ? -127 : ef - 127;
-    return min(100, max(-100, 14 - k));
-}
-
-typedef int i4_t __attribute__((ext_vector_type(4)));
-
-// Buffer resource (wave-uniform) over [base, base + elems): reads past it return 0.
+// Buffer resource (wave-uniform) over the elems elements from base: reads past it return 0 (elems may be <= 0)
 __device__ inline i4_t rsrc_from(const uint16_t* base, int64_t elems) {
-    int64_t bytes = elems * 2;
-    if (bytes > 0x7FFFFFF0LL) bytes = 0x7FFFFFF0LL;
-    if (bytes < 0) bytes = 0;
-    const uint64_t a = (uint64_t)base;
-    return i4_t{__builtin_amdgcn_readfirstlane((int)(uint32_t)a), __builtin_amdgcn_readfirstlane((int)((a >> 32) & 0xffff)),
-                __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000};
-}
-
-// One 16-B-per-lane LDS-DMA wave-instruction: LDS[lds_addr + 16 lane] = buffer[voff].  Inline asm on purpose: the
-// compiler tracks its own LDS-DMA builtins as pending writes to the whole staging array and then waits vmcnt(0)
-// before every ds_read of it, which drains the stages in flight; the ring's counted waits are done by hand instead.
-// Nothing else in these kernels uses M0.
-__device__ inline void dma16(i4_t r, uint32_t lds_addr, uint32_t voff) {
-    asm volatile("s_mov_b32 m0, %2\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds" ::"v"(voff), "s"(r), "s"(lds_addr)
-                 : "memory");
-}
-
-__device__ inline uint32_t lds_u32(const void* p) {
-    return __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(const lds_void_t*)p);
+    return dma_rsrc(base, max(elems * 2, (int64_t)0));
 }
 
 struct Tile {
@@ -360,7 +332,7 @@ __global__ __launch_bounds__(THREADS, 1) void gemm_kernel(Args a) {
             for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 
     float alpha_eff = a.alpha;
-    if constexpr (SPLIT) alpha_eff = __builtin_ldexpf(a.alpha, -(split_exp_pg(*a.p_max) + split_exp_pg(*a.q_max)));
+    if constexpr (SPLIT) alpha_eff = split_unscale(a.alpha, *a.p_max, *a.q_max);
 
     Frags f0, f1;
     read_frags<P_KC, Q_KC>(f0, lds, 0, wr, wq, lane);
@@ -530,12 +502,13 @@ __global__ __launch_bounds__(THREADS, 1) void gemm_kernel(Args a) {
 }  // namespace pg
 }  // namespace avse
 
+using namespace avse;
 using namespace avse::pg;
 
 // ------------------------------------------------------------------------------------------------ split planes
 // x (b, r, c) fp32, c contiguous -> hi / lo fp16 planes (rows hrs, batches hbs apart: x's strides, or a padded layout
 // whose rows are 16-B aligned for the GEMM's DMA): hi = fp16(x 2^e), lo = fp16(x 2^e - hi) with max |x| 2^e in
-// [2^14, 2^15) (dconv.hip's split, the same 22 significant bits); the planes' padding is not written.
+// [2^14, 2^15) (split16.h, the same 22 significant bits as the convolutions' operands); the planes' padding is not written.
 // Two streaming passes (max, then split): a workgroup takes rpb consecutive rows, float4 accesses when the rows are
 // 16-B aligned (VEC), the row's last c % 4 elements one by one; 4 accesses in flight per thread either way.  The max
 // pass of a contiguous x ignores the rows altogether (planes_absmax_flat_kernel).
@@ -554,23 +527,10 @@ __device__ inline int64_t planes_out_off(const PlanesArgs& a, int64_t row) {
     return (row / a.r) * a.hbs + (row % a.r) * a.hrs;
 }
 
-// grid-stride over the row blocks with a bounded grid of 1024-thread workgroups and one atomicMax per workgroup: the
-// max word is shared by every XCD, so its atomics serialise far from the CUs (~17 ns each: one per wave over 10^5 row
-// blocks cost 6.8 ms for a C3 activation, profiles/r05i_gemm_f32s_probe.jsonl; 2048 per call cost ~30 us of a 65 MB
-// pass), while 16 waves per CU keep enough loads in flight
+// grid-stride over the row blocks with a bounded grid of 1024-thread workgroups and one atomicMax per workgroup
+// (split16.h: one per wave over 10^5 row blocks cost 6.8 ms for a C3 activation, profiles/r05i_gemm_f32s_probe.jsonl;
+// 2048 per call cost ~30 us of a 65 MB pass), while 16 waves per CU keep enough loads in flight
 constexpr int AM_NT = 1024, AM_GRID = 256;
-
-__device__ inline void absmax_publish(float m, uint32_t* red, uint32_t* maxbits) {
-    uint32_t v = __float_as_uint(m);
-    for (int o = 32; o >= 1; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o, 64));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < AM_NT / 64; ++k) v = max(v, red[k]);
-        v = max(v, red[0]);
-        if (v) atomicMax(maxbits, v);
-    }
-}
 
 // the row walk (strided or padded x): tpr threads take a row, so AM_NT / tpr of the workgroup's rpb rows are in flight
 // at once (c = 64 floats left 16 of 1024 threads busy on one row at a time)
@@ -604,7 +564,7 @@ __global__ __launch_bounds__(AM_NT) void planes_absmax_kernel(PlanesArgs a, int6
             for (int u = 0; u < 4; ++u) m = fmaxf(m, fabsf(v[u]));
         }
     }
-    absmax_publish(m, red, a.maxbits);
+    block_max_publish<AM_NT / 64>(m, red, a.maxbits);
 }
 
 // contiguous x (16-B aligned): the flat array of n4 float4, grid-strided with 4 loads in flight per thread, whatever the
@@ -623,20 +583,12 @@ __global__ __launch_bounds__(AM_NT) void planes_absmax_flat_kernel(const float* 
             m = fmaxf(m, fmaxf(fmaxf(fabsf(v[u].x), fabsf(v[u].y)), fmaxf(fabsf(v[u].z), fabsf(v[u].w))));
     }
     if (blockIdx.x == 0 && 4 * n4 + threadIdx.x < n) m = fmaxf(m, fabsf(x[4 * n4 + threadIdx.x]));
-    absmax_publish(m, red, maxbits);
-}
-
-__device__ inline uint32_t split_pair(float x0, float x1, float sc, uint32_t& lo) {
-    const float s0 = x0 * sc, s1 = x1 * sc;
-    const _Float16 h0 = (_Float16)s0, h1 = (_Float16)s1;
-    const _Float16 l0 = (_Float16)(s0 - (float)h0), l1 = (_Float16)(s1 - (float)h1);
-    lo = (uint32_t)__builtin_bit_cast(uint16_t, l0) | ((uint32_t)__builtin_bit_cast(uint16_t, l1) << 16);
-    return (uint32_t)__builtin_bit_cast(uint16_t, h0) | ((uint32_t)__builtin_bit_cast(uint16_t, h1) << 16);
+    block_max_publish<AM_NT / 64>(m, red, maxbits);
 }
 
 template <bool VEC>
 __global__ __launch_bounds__(256) void planes_split_kernel(PlanesArgs a) {
-    const float sc = __builtin_ldexpf(1.f, split_exp_pg(*a.maxbits));
+    const float sc = split_scale(*a.maxbits);
     const int64_t c4 = VEC ? a.c / 4 : 0;
     for (int rr = 0; rr < a.rpb; ++rr) {
         const int64_t row = (int64_t)blockIdx.x * a.rpb + rr;
@@ -671,10 +623,7 @@ __global__ __launch_bounds__(256) void planes_split_kernel(PlanesArgs a) {
             for (int u = 0; u < 4; ++u) {
                 const int64_t i = i0 + u * 256;
                 if (i >= a.c) break;
-                const float w = v[u] * sc;
-                const _Float16 h = (_Float16)w;
-                a.hi[off + i] = h;
-                a.lo[off + i] = (_Float16)(w - (float)h);
+                split16(v[u] * sc, a.hi[off + i], a.lo[off + i]);
             }
         }
     }
@@ -685,7 +634,7 @@ __global__ __launch_bounds__(256) void planes_split_kernel(PlanesArgs a) {
 // consecutive addresses), 4 quadruples in flight; the pad columns c .. hrs - 1 are written as 0, so a GEMM may sum
 // over them (the time chunks of a weight gradient).
 __global__ __launch_bounds__(256) void planes_split_pad_kernel(PlanesArgs a) {
-    const float sc = __builtin_ldexpf(1.f, split_exp_pg(*a.maxbits));
+    const float sc = split_scale(*a.maxbits);
     const int64_t q4 = a.hrs / 4;                                  // quadruples per output row
     for (int rr = 0; rr < a.rpb; ++rr) {
         const int64_t row = (int64_t)blockIdx.x * a.rpb + rr;
@@ -781,14 +730,7 @@ __global__ __launch_bounds__(256) void add_max_kernel(int n4, int lp4, int l, co
             }
         }
     }
-    uint32_t v = __float_as_uint(m);
-    for (int o = 32; o >= 1; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o, 64));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        v = max(max(red[0], red[1]), max(red[2], red[3]));
-        if (v) atomicMax(maxbits, v);
-    }
+    block_max_publish<4>(m, red, maxbits);
 }
 
 static int cu_count_cached() {

@@ -7,6 +7,7 @@
 // the sum of squares reduced in registers with cross-lane adds: one HBM pass each way.
 // dweight is reduced per workgroup (grid-stride over rows) and summed by a second kernel.
 #include "common.h"
+#include "split16.h"
 
 namespace avse {
 namespace rms {
@@ -43,21 +44,11 @@ __device__ inline float wave_sum(float v) {
     return v;
 }
 
-// the workgroup's max |out| -> one atomicMax on the float bits (non-negative floats order like their bits): the
-// producer-side max of an operand the split-fp16 projection GEMMs split next (avse_split16_planes_known).  Per
-// workgroup, not per wave: the word's atomics serialise at the memory side (~17 ns each).  Called by every thread.
+// the workgroup's max |out| -> one atomicMax on the float bits (split16.h): the producer-side max of an operand the
+// split-fp16 projection GEMMs split next (avse_split16_planes_known).  Called by every thread.
 __device__ inline void block_max_out(float m, uint32_t* omax) {
     __shared__ uint32_t red[WPB];
-    uint32_t b = __float_as_uint(m);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) b = max(b, (uint32_t)__shfl_xor((int)b, o, 64));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = b;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int w = 0; w < WPB; ++w) b = max(b, red[w]);
-        if (b) atomicMax(omax, b);
-    }
+    block_max_publish<WPB>(m, red, omax);
 }
 
 template <typename TH, typename TY>

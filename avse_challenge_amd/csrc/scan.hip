@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "split16.h"
 
 namespace avse {
 namespace scan {
@@ -184,19 +185,12 @@ __device__ inline void load_bias_rows(float* bias_r, const float* bias, int d0, 
     for (int i = 0; i < RPT; ++i) bias_r[i] = (HAS_BIAS && d0 + wave + 4 * i < D) ? bias[d0 + wave + 4 * i] : 0.f;
 }
 
-// max |.| over the workgroup's 4 waves into *p as float bits (one vector atomic per workgroup -- same-word atomics
-// serialise far from the CUs; non-negative floats order as their bits): the producer-side max of an accumulated
-// output, for the split-fp16 GEMM that consumes it (round 6).  Every thread of the workgroup calls it.
+// max |.| over the workgroup's 4 waves into *p as float bits (split16.h; one vector atomic per workgroup): the
+// producer-side max of an accumulated output, for the split-fp16 GEMM that consumes it (round 6).  Every thread of
+// the workgroup calls it.  The atomic is unconditional here: a zero maximum is sent too.
 __device__ inline void block_absmax_to(float m, uint32_t* p) {
     __shared__ uint32_t s_mx[THREADS / 64];
-    uint32_t bits = __float_as_uint(m);
-    for (int o = 32; o >= 1; o >>= 1) bits = max(bits, (uint32_t)__shfl_xor((int)bits, o, 64));
-    if ((threadIdx.x & 63) == 0) s_mx[threadIdx.x >> 6] = bits;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < THREADS / 64; ++w) bits = max(bits, s_mx[w]);
-        atomicMax(p, bits);
-    }
+    block_max_publish<THREADS / 64, true>(m, s_mx, p);
 }
 
 // ------------------------------------------------------------------------------- forward

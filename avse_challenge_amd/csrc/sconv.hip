@@ -28,15 +28,14 @@
 
 #include "bnact_cols.h"
 #include "common.h"
+#include "split16.h"
 
 namespace avse {
 namespace scv {
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef int i4_t __attribute__((ext_vector_type(4)));
 typedef short s4_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __attribute__((address_space(3))) s4_t lds_s4_t;
 
 constexpr int ROWB = 64;                 // LDS / Q bytes per staged (position, 16-channel chunk)
@@ -45,32 +44,6 @@ constexpr int XIMG = NPOS_MAX * ROWB;    // 45 KB
 constexpr uint32_t OOB = 0x7FFFFFF0u;    // DMA offset past every buffer range: lands as zeros
 
 __device__ inline int swz(int r) { return (r >> 2) & 3; }
-
-// same function as dconv.hip / projgemm.hip: max |x| 2^e in [2^14, 2^15)
-__device__ inline int split_exp(uint32_t mb) {
-    const int ef = (int)((mb >> 23) & 0xff);
-    if (mb == 0) return 0;
-    const int k = ef == 0 ? -127 : ef - 127;
-    return min(100, max(-100, 14 - k));
-}
-
-__device__ inline i4_t rsrc_of(const void* base, int64_t bytes) {
-    if (bytes > 0x7FFFFFF0LL) bytes = 0x7FFFFFF0LL;
-    const uint64_t a = (uint64_t)base;
-    return i4_t{__builtin_amdgcn_readfirstlane((int)(uint32_t)a), __builtin_amdgcn_readfirstlane((int)((a >> 32) & 0xffff)),
-                __builtin_amdgcn_readfirstlane((int)bytes), 0x00020000};
-}
-
-// one 16-B-per-lane LDS-DMA wave-instruction (inline asm: the builtin makes the compiler wait vmcnt(0) before every
-// ds_read of the array).  Nothing else in these kernels uses M0.
-__device__ inline void dma16(i4_t r, uint32_t lds_addr, uint32_t voff) {
-    asm volatile("s_mov_b32 m0, %2\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds" ::"v"(voff), "s"(r), "s"(lds_addr)
-                 : "memory");
-}
-
-__device__ inline uint32_t lds_u32(const void* p) {
-    return __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(const lds_void_t*)p);
-}
 
 __device__ inline half8 frag(const uint8_t* img, int row, int c) {
     return *reinterpret_cast<const half8*>(img + row * ROWB + 16 * (c ^ swz(row)));
@@ -115,8 +88,8 @@ __global__ __launch_bounds__(512, 1) void fwd_kernel(FArgs a) {
     const int NHWo = a.N * a.Ho * a.Wo, NHo = a.N * a.Ho;
     const int g0 = p0 / a.Wo;                                      // first output row (flat n, ho) of the tile
     const int NQ = a.Ci / 16, NSTG = 3 * NQ;
-    const i4_t rx = rsrc_of(a.xq, (int64_t)a.N * a.Hi * a.Wi * a.Ci * 4);
-    const i4_t rw = rsrc_of(a.wq, (int64_t)9 * a.Ci * a.Co * 4);
+    const i4_t rx = dma_rsrc(a.xq, (int64_t)a.N * a.Hi * a.Wi * a.Ci * 4);
+    const i4_t rw = dma_rsrc(a.wq, (int64_t)9 * a.Ci * a.Co * 4);
     const uint32_t lds0 = lds_u32(lds);
     const int PX = a.npos / 16, PT = PX + PW;
     const int npieces = (PT - wave + WAVES - 1) / WAVES;
@@ -223,7 +196,7 @@ __global__ __launch_bounds__(512, 1) void fwd_kernel(FArgs a) {
 
     // epilogue: acc[i][j] register 4 g + e = pixel p0 + 64 wm + 32 i + 8 g + 4 (lane >> 5) + e, channel
     // o0 + 64 wn + 32 j + (lane & 31): 32 lanes write 128 contiguous bytes of one pixel
-    const float scale = __builtin_ldexpf(1.f, -(split_exp(*a.xmax) + split_exp(*a.wmax)));
+    const float scale = split_unscale(1.f, *a.xmax, *a.wmax);
     auto store = [&](int j) {
         const int o = o0 + 64 * wn + 32 * j + (lane & 31);
 #pragma unroll
@@ -294,8 +267,8 @@ __device__ __forceinline__ void dgrad2_body(const DArgs& a, int slot, int tile, 
     const int NP = a.N * Ha * Wb, NHa = a.N * Ha;
     const int g0 = p0 / Wb;
     const int NQ = a.I / 16, NSTG = NTH * NQ;
-    const i4_t rx = rsrc_of(a.dyq, (int64_t)a.N * a.Ho * a.Wo * a.I * 4);
-    const i4_t rw = rsrc_of(a.wq, (int64_t)9 * a.I * a.O * 4);
+    const i4_t rx = dma_rsrc(a.dyq, (int64_t)a.N * a.Ho * a.Wo * a.I * 4);
+    const i4_t rw = dma_rsrc(a.wq, (int64_t)9 * a.I * a.O * 4);
     const uint32_t lds0 = lds_u32(lds);
     const int PX = a.npos[slot] / 16, PT = PX + PW;
     const int npieces = (PT - wave + WAVES - 1) / WAVES;
@@ -396,7 +369,7 @@ __device__ __forceinline__ void dgrad2_body(const DArgs& a, int slot, int tile, 
     }
 
     // epilogue: phase pixel p -> dX pixel (n, 2 ar + py, 2 b + px); 4 consecutive phase pixels per (i, g)
-    const float scale = __builtin_ldexpf(1.f, -(split_exp(*a.dymax) + split_exp(*a.wmax)));
+    const float scale = split_unscale(1.f, *a.dymax, *a.wmax);
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -506,8 +479,8 @@ __global__ __launch_bounds__(512, 1) void wgrad_kernel(WArgs a) {
     const int r = t / a.nob;
     const int c_lo = (int)((int64_t)r * a.chunks / a.ranges), c_hi = (int)((int64_t)(r + 1) * a.chunks / a.ranges);
     const int NHWo = a.N * a.Ho * a.Wo, NHo = a.N * a.Ho;
-    const i4_t rx = rsrc_of(a.xq, (int64_t)a.N * a.Hi * a.Wi * a.Ci * 4);
-    const i4_t ry = rsrc_of(a.dyq, (int64_t)NHWo * a.Co * 4);
+    const i4_t rx = dma_rsrc(a.xq, (int64_t)a.N * a.Hi * a.Wi * a.Ci * 4);
+    const i4_t ry = dma_rsrc(a.dyq, (int64_t)NHWo * a.Co * 4);
     const uint32_t lds0 = lds_u32(lds);
     const int PT = PY + a.npw / 4;
     const int npieces = (PT - wave + WAVES - 1) / WAVES;
@@ -653,7 +626,7 @@ __global__ __launch_bounds__(512, 1) void wgrad_kernel(WArgs a) {
     }
     // partial tiles: acc[t][kw] register 4 q + e = row o = OB ob + 64 obw + 32 t + 8 q + 4 (lane >> 5) + e, column
     // i = 64 ib + 32 ibw + (lane & 31)
-    const float sc = __builtin_ldexpf(1.f, -(split_exp(*a.xmax) + split_exp(*a.dymax)));
+    const float sc = split_unscale(1.f, *a.xmax, *a.dymax);
     float* pp = a.part + ((int64_t)(r * KG + kg) * 9 + kh * 3) * a.Co * a.Ci;
 #pragma unroll
     for (int t = 0; t < 2; ++t)
@@ -694,14 +667,7 @@ __global__ void wmax_kernel(const float* w, int n, uint32_t* out) {
     __shared__ uint32_t red[4];
     float m = 0.f;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) m = fmaxf(m, fabsf(w[i]));
-    uint32_t b = __float_as_uint(m);
-    for (int o = 32; o >= 1; o >>= 1) b = max(b, (uint32_t)__shfl_xor((int)b, o, 64));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = b;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        b = max(max(red[0], red[1]), max(red[2], red[3]));
-        if (b) atomicMax(out, b);
-    }
+    block_max_publish<4>(m, red, out);
 }
 
 // W (Co, Ci, 3, 3) fp32 -> [kh][q][kw][o][hi 16 | lo 16]; transposed: the input gradient's W'[o = ci][i = co][kh][kw] =
@@ -709,7 +675,7 @@ __global__ void wmax_kernel(const float* w, int n, uint32_t* out) {
 __global__ void wsplit_kernel(const float* w, int Co, int Ci, int transposed, const uint32_t* maxbits, uint16_t* wq) {
     const int O = transposed ? Ci : Co, I = transposed ? Co : Ci, NQ = I / 16;
     const int64_t total = (int64_t)9 * O * I;
-    const float sc = __builtin_ldexpf(1.f, split_exp(*maxbits));
+    const float sc = split_scale(*maxbits);
     for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
         const int c = (int)(e % 16);
         const int64_t rrow = e / 16;                            // ((kh NQ + q) 3 + kw) O + o
@@ -717,10 +683,7 @@ __global__ void wsplit_kernel(const float* w, int Co, int Ci, int transposed, co
         const int kh = s / NQ, q = s % NQ, i = q * 16 + c;
         const float v = transposed ? w[(((int64_t)i * Ci + o) * 3 + (2 - kh)) * 3 + (2 - kw)]
                                    : w[(((int64_t)o * Ci + i) * 3 + kh) * 3 + kw];
-        const float sv = v * sc;
-        const _Float16 h = (_Float16)sv, l = (_Float16)(sv - (float)h);
-        wq[rrow * 32 + c] = __builtin_bit_cast(uint16_t, h);
-        wq[rrow * 32 + 16 + c] = __builtin_bit_cast(uint16_t, l);
+        split16(v * sc, wq[rrow * 32 + c], wq[rrow * 32 + 16 + c]);
     }
 }
 
@@ -730,7 +693,7 @@ __global__ void wsplit_dgrad2_kernel(const float* w, int Co, int Ci, const uint3
     const int O = Ci, NQ = Co / 16;
     const int64_t tap = (int64_t)O * Co;                        // (o, i) elements per tap
     const int64_t total = 9 * tap;
-    const float sc = __builtin_ldexpf(1.f, split_exp(*maxbits));
+    const float sc = split_scale(*maxbits);
     for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
         const int c = (int)(e % 16);
         const int64_t rrow = e / 16;                            // row of 16 channels over the whole image
@@ -745,10 +708,7 @@ __global__ void wsplit_dgrad2_kernel(const float* w, int Co, int Ci, const uint3
         const int q = (int)(sq % NQ), th = (int)(sq / NQ);
         const int kh = py ? (th ? 2 : 0) : 1, kw = px ? (tw ? 2 : 0) : 1;
         const int i = q * 16 + c;
-        const float sv = w[(((int64_t)i * Ci + o) * 3 + kh) * 3 + kw] * sc;
-        const _Float16 h = (_Float16)sv, l = (_Float16)(sv - (float)h);
-        wq[rrow * 32 + c] = __builtin_bit_cast(uint16_t, h);
-        wq[rrow * 32 + 16 + c] = __builtin_bit_cast(uint16_t, l);
+        split16(w[(((int64_t)i * Ci + o) * 3 + kh) * 3 + kw] * sc, wq[rrow * 32 + c], wq[rrow * 32 + 16 + c]);
     }
 }
 

@@ -617,8 +617,10 @@ def conv3d_fwd(x, w, return_xmax=False):
                             stream_ptr(x.device)), "avse_conv3d_fwd")
     if not return_xmax:
         return y
-    # workspace: the split weights (2 * Cin * 5 * 8192 bytes), then max |W|, max |x| (conv3d_fwd.hip ws_bytes)
-    xmax = ws.view(torch.int32)[(2 * Cin * 5 * 8192) // 4 + 1:(2 * Cin * 5 * 8192) // 4 + 2]
+    off = L.avse_conv3d_fwd_xmax_offset(Cin, H, W)      # where the forward's absmax pass left max |x| (conv3d_fwd.hip)
+    if off <= 0 or off % 4 != 0 or off + 4 > nb:
+        raise RuntimeError(f"conv3d_fwd: max |x| word at byte {off} of a {nb}-byte workspace")
+    xmax = ws.view(torch.int32)[off // 4:off // 4 + 1]
     return y, (xmax if x.dtype == torch.float32 else None)
 
 

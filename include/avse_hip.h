@@ -264,8 +264,11 @@ int avse_istft(int64_t batch, int64_t frames, int64_t length, const float* mag, 
  * x: (B, CIN, T, H, W) contiguous, x_dtype AVSE_U8 (the raw uint8 frames) or AVSE_F32; w: (64, CIN, 5, 7, 7) fp32;
  * y: (B, 64, T, HO, WO) fp32 with HO = (H - 1) / 2 + 1.  Compiled shapes: CIN 3, 96 x 96 and CIN 1, 112 x 112
  * (workspace_bytes returns 0 for any other; the call then returns AVSE_ESHAPE).  workspace: the split weights
- * (2 * CIN * 5 * 8192 bytes), then max |W| and max |x| as float bits (uint32 words 0 and 1), then scratch. */
+ * (2 * CIN * 5 * 8192 bytes), then max |W| and max |x| as float bits (uint32 words 0 and 1), then scratch.
+ * xmax_offset: the byte offset of the max |x| word inside the workspace (what an fp32 forward leaves there is the
+ * xmax of avse_conv3d_wgrad_split); <= 0 for a shape that is not compiled in. */
 int64_t avse_conv3d_fwd_workspace_bytes(int64_t CIN, int64_t H, int64_t W);
+int64_t avse_conv3d_fwd_xmax_offset(int64_t CIN, int64_t H, int64_t W);
 int avse_conv3d_fwd(int64_t B, int64_t CIN, int64_t T, int64_t H, int64_t W, int32_t x_dtype, const void* x,
                     const float* w, float* y, float* workspace, avse_stream_t stream);
 

@@ -34,6 +34,20 @@ def test_library_exports_every_declared_symbol():
 
 
 @needs_lib
+def test_conv3d_fwd_xmax_offset():
+    """The max |x| word kernels.conv3d_fwd(return_xmax=True) reads: a word inside the workspace, at the present layout
+    (the split weights, 2 * CIN * 5 * 8192 bytes, then max |W|, then max |x|)."""
+    from avse_challenge_amd import _lib
+    L = _lib.lib()
+    for cin, h, w in ((3, 96, 96), (1, 112, 112)):
+        off = L.avse_conv3d_fwd_xmax_offset(cin, h, w)
+        assert off > 0 and off % 4 == 0
+        assert off <= L.avse_conv3d_fwd_workspace_bytes(cin, h, w) - 4
+        assert off == 2 * cin * 5 * 8192 + 4
+    assert L.avse_conv3d_fwd_xmax_offset(2, 96, 96) <= 0
+
+
+@needs_lib
 def test_host_side_validation_without_gpu():
     from avse_challenge_amd import _lib
     L = _lib.lib()

@@ -24,7 +24,7 @@ def K():
 
 
 def _q_decode(t):
-    """A split-output (N, C, H, W) tensor -> fp64 values (hi + lo) 2^-e, e from its bound (dconv.hip split_exp)."""
+    """A split-output (N, C, H, W) tensor -> fp64 values (hi + lo) 2^-e, e from its bound (split16.h split_exp)."""
     q = K().q_view(t).view(torch.float16).reshape(-1, t.shape[1] // 16, 2, 16).double()
     bits = int(getattr(t, K().ABSMAX_ATTR).item())
     e = max(-100, min(100, 14 - (((bits >> 23) & 0xFF) - 127))) if bits else 0

@@ -1,7 +1,7 @@
 """The split-fp16 kernels across the dynamic range of their power-of-two scale.
 
 Every split consumer scales an operand by 2^e, e = clamp(14 - floor(log2 max|x|), -100, 100) (``split_exp`` in
-csrc/dconv.hip and its copies), splits it into fp16 hi + lo and undoes the scale in the epilogue with
+csrc/split16.h), splits it into fp16 hi + lo and undoes the scale in the epilogue with
 ``ldexpf(1, -(e1 + e2))``.  The scale is a power of two, so the following hold exactly and are asserted with
 ``torch.equal``, no tolerance:
 
