@@ -243,6 +243,13 @@ SIGNATURES = {
     "avse_sconv_wgrad": (c_i32, [c_i64] * 6 + [c_vp] * 7),
     "avse_sconv_dgrad2_supported": (c_i32, [c_i64] * 5),
     "avse_sconv_dgrad2": (c_i32, [c_i64] * 5 + [c_vp] * 6),
+    # MBSTOI scoring in fp64 (evaluation/avse4/mbstoi/mbstoi.py:31-334, mbstoi_utils.py:17-224, :361-540)
+    "avse_mbstoi_frames": (c_i64, [c_i64]),
+    "avse_mbstoi_workspace_bytes": (c_i64, [c_i64, c_i64]),
+    "avse_mbstoi_gate": (c_i32, [c_i64, c_i64] + [c_vp] * 7),
+    "avse_mbstoi_bands": (c_i32, [c_i64, c_i64] + [c_vp] * 6),
+    "avse_mbstoi_ec": (c_i32, [c_i64, c_i64, c_vp, c_i32, c_i64, c_i64] + [c_vp] * 8),
+    "avse_mbstoi_score": (c_i32, [c_i64, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp]),
 }
 
 _lib = None

@@ -384,6 +384,15 @@ class AVSE4BaselineModule(nn.Module):
         return load_lightning_checkpoint(cls, checkpoint_path, map_location, strict, **kwargs)
 
     @torch.no_grad()
+    def mbstoi(self, batch, sr=16000):
+        """The challenge's ranking metric (evaluation/avse4/objective_evaluation.py:60-69) of a validation batch, on the
+        GPU: forward, peak-normalise each utterance as enhance does, score against batch["clean"]; (B,) fp64."""
+        from . import metrics
+        est = self(batch)
+        est = est / est.abs().amax(dim=(1, 2), keepdim=True)
+        return metrics.mbstoi(batch["clean"], est, sr=sr)
+
+    @torch.no_grad()
     def enhance(self, data):
         """model.py:335-352: forward one utterance and peak-normalise (returns numpy arrays)."""
         dev = next(self.parameters()).device

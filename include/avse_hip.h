@@ -660,6 +660,46 @@ int avse_dconv_wgrad16(int64_t N, int64_t H, int64_t W, int64_t dil, const void*
                        const void* dyq, const uint32_t* dymax, float* dw, float* db, float* workspace,
                        avse_stream_t stream);
 
+/* ---------------------------------------------------------------- MBSTOI scoring (fp64) ------
+ * The binaural intelligibility metric the AVSE-4 challenge ranks by (evaluation/avse4/objective_evaluation.py:60-69,
+ * mbstoi/mbstoi.py:31-334 with its defaults: 10 kHz, frame 256, hop 128, FFT 512, 15 third-octave bands from 150 Hz,
+ * segments of 30 frames, 40 dB dynamic range), after the resampling of mbstoi.py:107-124, which the caller does.
+ * sig: (batch, 4, max_len) fp64, rows clean left, clean right, processed left, processed right; len[b] <= max_len
+ * is utterance b's own sample count (device int32).  F = avse_mbstoi_frames(max_len) = len(range(0, max_len - 256,
+ * 128)) frame slots per utterance (exclusive end: 256 + 128 k samples give k frames).  window: the 256 doubles
+ * hanning(258)[1:-1].  Everything stays on the device; no entry point synchronises.  No float atomics: the same bits
+ * from run to run, and for an utterance alone as inside a batch. */
+int64_t avse_mbstoi_frames(int64_t len);
+/* bytes of avse_mbstoi_gate's workspace (the frame energies) */
+int64_t avse_mbstoi_workspace_bytes(int64_t batch, int64_t max_len);
+/* Silent-frame gate (mbstoi_utils.py:392-484): frame energies 20 log10(|windowed frame| + eps) of the two clean ears, a
+ * frame is kept if max - 40 - e < 0 for either ear.  kept (batch, F) int32: the kept frame indices in ascending order,
+ * then -1; count (batch) int32: K[b], how many. */
+int avse_mbstoi_gate(int64_t batch, int64_t max_len, const double* sig, const int32_t* len, const double* window,
+                     double* workspace, int32_t* kept, int32_t* count, avse_stream_t stream);
+/* STFT of the re-stitched signals (mbstoi_utils.py:361-389 on the overlap-add of :471-482; K kept frames give K - 1 STFT
+ * frames) reduced to the third-octave bands of thirdoct (:487-540): bq (batch, F - 1, 15, 8) fp64 = PL, PR, Re rho,
+ * Im rho of the clean pair, then of the processed pair, with PL = sum |X_L|^2, PR = sum |X_R|^2, rho = sum conj(X_R)
+ * X_L over the band's bins (the quantities of :126-143); frames from K[b] - 1 on are written as zeros.  F >= 2. */
+int avse_mbstoi_bands(int64_t batch, int64_t max_len, const double* sig, const double* window, const int32_t* kept,
+                      const int32_t* count, double* bq, avse_stream_t stream);
+/* Equalisation-cancellation grid search (mbstoi_utils.py:17-224) and better-ear selection (mbstoi.py:279-329) per cell
+ * (utterance, band, segment j of frames j .. j + 29).  bq (batch, frame_slots, 15, 8); utterance b has
+ * frames[b] - frames_offset STFT frames (frames_offset 1: frames = the gate's count K; 0: a frame count).
+ * tau_table (15, n_taus, 6): cos(w tau), -sin(w tau), cos(2 w tau), -sin(2 w tau), deltexp, exp(-w^2 sigma_delta^2 / 2);
+ * gamma_table (n_gammas, 6): 10^g, 10^-g, 10^2g, 10^-2g, epsexp, exp(ln(10)^2 sigma_eps^2 / 2) (mbstoi.py:200-212,
+ * mbstoi_utils.py:78-95), n_gammas <= 64.  d (batch, 15, frame_slots - 29): the intermediate correlation after the
+ * better-ear selection, 0 outside the utterance's own frames[b] - frames_offset - 29 segments.  Optional, same
+ * shape: d_ec (before the selection), p_ec (p_ec_max), winner (int32, tau index * n_gammas + gamma index of the first
+ * maximum in the reference's order; -1 where the `-1` rule of :208 fired or outside the utterance). */
+int avse_mbstoi_ec(int64_t batch, int64_t frame_slots, const int32_t* frames, int32_t frames_offset, int64_t n_taus,
+                   int64_t n_gammas, const double* bq, const double* tau_table, const double* gamma_table, double* d,
+                   double* d_ec_or_null, double* p_ec_or_null, int32_t* winner_or_null, avse_stream_t stream);
+/* score (batch) fp64: the mean of d over the utterance's own 15 x segments cells (mbstoi.py:330), NaN with none, summed
+ * in an order that depends on the utterance's segment count alone. */
+int avse_mbstoi_score(int64_t batch, int64_t frame_slots, const int32_t* frames, int32_t frames_offset, const double* d,
+                      double* score, avse_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
