@@ -203,6 +203,12 @@ SIGNATURES = {
     "avse_dwconv_gln_fwd": (c_i32, [c_i64] * 5 + [c_vp] * 5 + [c_f32] + [c_vp] * 5),
     "avse_dwconv_gln_fwd_q": (c_i32, [c_i64] * 5 + [c_vp] * 5 + [c_f32] + [c_vp] * 3 + [c_i64] + [c_vp] * 4),
     "avse_dwconv_gln_bwd": (c_i32, [c_i64] * 5 + [c_vp] * 14),
+    # length-aware forwards for ragged inference batches (lengths: device int32, one per sample)
+    "avse_prelu_gln_fwd_len": (c_i32, [c_i64] * 3 + [c_vp] * 5 + [c_f32] + [c_vp] * 4),
+    "avse_dwconv_gln_fwd_len": (c_i32, [c_i64] * 5 + [c_vp] * 6 + [c_f32] + [c_vp] * 5),
+    "avse_dwconv_gln_fwd_q_len": (c_i32, [c_i64] * 5 + [c_vp] * 6 + [c_f32] + [c_vp] * 3 + [c_i64] + [c_vp] * 4),
+    "avse_dwconv_fwd_len": (c_i32, [c_i64] * 5 + [c_vp] * 5),
+    "avse_upsample_linear_len": (c_i32, [c_i64] * 5 + [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp]),
     "avse_lstm_padded_hidden": (c_i64, [c_i64]),
     "avse_lstm_group_size": (c_i64, [c_i64, c_i64]),
     "avse_lstm_group_workspace_bytes": (c_i64, [c_i64, c_i64]),

@@ -109,6 +109,10 @@ def _pw(conv, x, dy_planes=False):
     return _PointwiseFn.apply(conv.weight[:, :, 0], x, dy_planes)
 
 
+def _as_lengths(lengths, device):
+    return lengths if isinstance(lengths, K.Lengths) else K.Lengths(lengths, device)
+
+
 _INTERP = {}
 
 
@@ -159,6 +163,13 @@ class DepthwiseSeparableConv(nn.Module):
         y = dwconv_prelu_gln(x, dw.weight, pr.weight, nm.gamma, nm.beta, self.dilation, planes=planes)
         return _pw(pw, y)
 
+    def forward_ragged(self, x, lengths):
+        dw, pr, nm, pw = self.net
+        planes = _pw_split_ok(pw.weight[:, :, 0], x)
+        y = K.dwconv_gln_fwd(x, dw.weight, self.dilation, pr.weight, nm.gamma.reshape(-1), nm.beta.reshape(-1),
+                             planes=planes, lengths=lengths)[0]
+        return _pw(pw, y)
+
 
 class _ResidualAddFn(torch.autograd.Function):
     """y = a + b (TemporalBlock's residual, model.py:268) as one pass that also keeps max |y| (kernels.add_max_flat):
@@ -189,6 +200,16 @@ class TemporalBlock(nn.Module):
             return _ResidualAddFn.apply(out, x)
         return out + x
 
+    def forward_ragged(self, x, lengths):
+        """forward for a ragged batch whose x is 0 past lengths[b] (inference): both gLN sites on the length-aware
+        kernels, so the output is 0 there again (the 1x1 convs have no bias, the residual adds zeros)."""
+        c1, pr, nm, ds = self.net
+        y = K.prelu_gln_fwd(_pw(c1, x), pr.weight, nm.gamma.reshape(-1), nm.beta.reshape(-1), lengths=lengths)[0]
+        out = ds.forward_ragged(y, lengths)
+        if _pw_split_ok(c1.weight[:, :, 0], x) and K.add_max_flat_ok(out, x):
+            return K.add_max_flat(out, x)
+        return out + x
+
 
 class VisualConv1D(nn.Module):
     def __init__(self, c=512):
@@ -201,6 +222,15 @@ class VisualConv1D(nn.Module):
         _, bn1, dw, pr, bn2, pw = self.net
         y = dwconv1d(bn1(F.relu(x)), dw.weight, 1)
         y = bn2(_PReLUFn.apply(y, pr.weight))
+        return _pw(pw, y) + x
+
+    def forward_ragged(self, x, valid, vis_lengths):
+        """forward for a ragged batch whose x is 0 past vis_lengths[b] (valid: that mask, (B, 1, Tv)); so is the
+        output.  The depthwise conv reads bn1's shift in the padding frames as 0; bn2's is selected away before the 1x1
+        conv's absmax pass."""
+        _, bn1, dw, pr, bn2, pw = self.net
+        y = K.dwconv_fwd(bn1(F.relu(x)), dw.weight, 1, lengths=vis_lengths)
+        y = torch.where(valid, bn2(_PReLUFn.apply(y, pr.weight)), 0.0)
         return _pw(pw, y) + x
 
 
@@ -232,6 +262,32 @@ class TemporalConvNet(nn.Module):
                 x = blk(x)
         x = F.relu(_pw(self.mask_conv1x1, x))
         return x.reshape(bsz, self.num_channels, Bc, K)
+
+    def forward_ragged(self, x, visual, lengths, vis_lengths):
+        """forward for a zero-padded ragged batch (inference): x (B, N, Kmax) is 0 past lengths[b] frames, visual
+        (B, Tvmax, 512) past vis_lengths[b] video frames (both kernels.Lengths).  Every tensor a temporal kernel or an
+        absmax pass reads keeps exact zeros there, so sample b's mask equals forward() on it alone; the
+        mask is 0 past lengths[b]."""
+        dev = x.device
+        kvalid = (torch.arange(x.shape[-1], device=dev) < lengths.dev[:, None])[:, None]
+        vvalid = (torch.arange(visual.shape[1], device=dev) < vis_lengths.dev[:, None])[:, None]
+        visual = visual.transpose(1, 2)
+        for vc in self.visual_conv:
+            visual = vc.forward_ragged(visual, vvalid, vis_lengths)
+        # the cLN bias is selected away in the padding frames; the bias-free bottleneck then leaves them 0
+        x = _pw(self.bottleneck_conv1x1, torch.where(kvalid, self.layer_norm(x), 0.0))
+        bsz, Bc, Kn = x.shape
+        for i in range(len(self.tcn)):
+            v = _pw(self.ve_conv1x1[i], visual)
+            seq = self.tcn[i]
+            xv = torch.empty(bsz, 2 * Bc, Kn, device=dev, dtype=torch.float32)    # torch.cat((x, v), 1): v lands in place
+            xv[:, :Bc] = x
+            K.upsample_linear_len(v, vis_lengths, lengths, self.up, xv[:, Bc:])
+            x = _pw(seq[0], xv)
+            for blk in list(seq)[1:]:
+                x = blk.forward_ragged(x, lengths)
+        x = F.relu(_pw(self.mask_conv1x1, x))
+        return x.reshape(bsz, self.num_channels, Bc, Kn)
 
 
 class Encoder(nn.Module):
@@ -277,6 +333,27 @@ class Separator(nn.Module):
     def forward(self, mixture, visual):
         w = self.encoder(mixture)
         est = self.decoder(w, self.separator(w, visual))
+        return F.pad(est, (0, mixture.shape[-1] - est.shape[-1]))
+
+    @torch.no_grad()
+    def forward_ragged(self, mixture, visual, lengths, vis_lengths):
+        """Inference on a padded batch of utterances of different lengths: mixture (B, C, Tmax) with lengths[b] valid
+        samples, visual (B, Tvmax, 512) from VisualFrontend.forward_ragged with vis_lengths[b] valid frames.  Row b of
+        the result equals forward() on utterance b alone (to the rounding of the batch-wide split-fp16 scales) and is 0
+        from 20 (K_b - 1) + 40 on (the reference's F.pad), K_b = (lengths[b] - L) // (L // 2) + 1.  What the padding
+        of mixture holds, NaN and Inf included, is not used."""
+        L, hop = self.encoder.L, self.encoder.L // 2
+        dev = mixture.device
+        tl = _as_lengths(lengths, dev).checked(mixture.shape[0], mixture.shape[-1], "forward_ragged (lengths)")
+        if min(tl.host) < L:
+            raise ValueError(f"forward_ragged: every utterance needs at least {L} samples, got {min(tl.host)}")
+        kl = K.Lengths([(t - L) // hop + 1 for t in tl.host], dev)
+        vl = _as_lengths(vis_lengths, dev).checked(visual.shape[0], visual.shape[1], "forward_ragged (vis_lengths)")
+        tvalid = (torch.arange(mixture.shape[-1], device=dev) < tl.dev[:, None])[:, None]
+        kvalid = (torch.arange((mixture.shape[-1] - L) // hop + 1, device=dev) < kl.dev[:, None])[:, None]
+        # the frame past an utterance's last still overlaps valid samples: selected away, with the padding frames
+        w = torch.where(kvalid, self.encoder(torch.where(tvalid, mixture.float(), 0.0)), 0.0)
+        est = self.decoder(w, self.separator.forward_ragged(w, visual, kl, vl))
         return F.pad(est, (0, mixture.shape[-1] - est.shape[-1]))
 
 
@@ -341,9 +418,22 @@ class VisualFrontend(nn.Module):
         return self
 
     def forward(self, x):                                   # (B, 1, T, 112, 112) -> (B, T, 512)
+        return self._features((x - NORM_MEAN) / NORM_STD)
+
+    @torch.no_grad()
+    def forward_ragged(self, x, vis_lengths):
+        """forward for a padded batch of clips with vis_lengths[b] valid frames (inference): the normalised frames past
+        them are selected to 0 -- what the Conv3d's own zero padding in time is for a clip alone -- and so are the
+        features there.  Frames are independent after the Conv3d, so clip b's valid features equal forward() on it."""
+        vl = _as_lengths(vis_lengths, x.device).checked(x.shape[0], x.shape[2], "VisualFrontend.forward_ragged")
+        valid = torch.arange(x.shape[2], device=x.device) < vl.dev[:, None]                  # (B, Tv)
+        y = self._features(torch.where(valid[:, None, :, None, None], (x.float() - NORM_MEAN) / NORM_STD, 0.0))
+        return torch.where(valid[:, :, None], y, 0.0)
+
+    def _features(self, x):                                 # normalised frames -> (B, T, 512)
         bsz = x.shape[0]
         conv, bn, _, pool = self.frontend3D
-        y = conv((x - NORM_MEAN) / NORM_STD)
+        y = conv(x)
         if self.channels_last:
             y = bn_act_pool_frames(y, bn, "relu", pool, bn_act)
         else:
@@ -401,3 +491,54 @@ class AVSE4BaselineModule(nn.Module):
         est = self(inputs)[0].cpu().numpy()
         est /= np.max(np.abs(est))
         return np.asarray(data["clean"]), np.asarray(data["noisy_audio"]), est
+
+    @torch.no_grad()
+    def enhance_batch(self, items):
+        """enhance() for a list of utterances of different lengths in one forward: items are dicts as enhance takes
+        (noisy_audio (C, T_b), vis_feat (1, Tv_b, 112, 112), optionally clean); returns the list of enhance()'s
+        (clean, noisy, estimate) triples, each estimate cropped to T_b and peak-normalised over its own samples.  One
+        padded upload, one ragged forward (Separator.forward_ragged), one download."""
+        if not items:
+            return []
+        dev = next(self.parameters()).device
+        noisy = [np.asarray(d["noisy_audio"], dtype=np.float32) for d in items]
+        vis = [np.asarray(d["vis_feat"], dtype=np.float32) for d in items]
+        tl, vl = [a.shape[-1] for a in noisy], [v.shape[1] for v in vis]
+        audio = np.zeros((len(items), noisy[0].shape[0], max(tl)), np.float32)
+        video = np.zeros((len(items), 1, max(vl)) + vis[0].shape[2:], np.float32)
+        for b, (a, v) in enumerate(zip(noisy, vis)):
+            audio[b, :, :tl[b]] = a
+            video[b, :, :vl[b]] = v
+        vlen = K.Lengths(vl, dev)
+        feats = self.visual_frontend.forward_ragged(torch.from_numpy(video).to(dev), vlen)
+        est = self.model.forward_ragged(torch.from_numpy(audio).to(dev), feats, tl, vlen).cpu().numpy()
+        out = []
+        for b, d in enumerate(items):
+            e = est[b, :, :tl[b]].copy()
+            e /= np.max(np.abs(e))
+            out.append((np.asarray(d.get("clean")) if d.get("clean") is not None else None,
+                        np.asarray(d["noisy_audio"]), e))
+        return out
+
+
+def plan_ragged_batches(lengths, batch_size, max_pad_ratio=1.25):
+    """Batches for enhance_batch: the indices of `lengths` sorted by length and cut greedily so that a batch holds at
+    most batch_size items and its padded size max(len) * n stays within max_pad_ratio of its useful size sum(len).
+    Every index appears exactly once; an item no neighbour fits with is a batch of its own (ratio 1).  Host code; the
+    ratio is a setting, not a claim about speed."""
+    if batch_size < 1 or max_pad_ratio < 1.0:
+        raise ValueError("plan_ragged_batches: batch_size >= 1 and max_pad_ratio >= 1")
+    lengths = [int(v) for v in lengths]
+    if any(v < 1 for v in lengths):
+        raise ValueError("plan_ragged_batches: lengths must be positive")
+    batches, cur, total = [], [], 0
+    for i in sorted(range(len(lengths)), key=lambda j: (lengths[j], j)):
+        n = lengths[i]                                       # ascending: the newcomer is the batch's longest
+        if cur and (len(cur) == batch_size or n * (len(cur) + 1) > max_pad_ratio * (total + n)):
+            batches.append(cur)
+            cur, total = [], 0
+        cur.append(i)
+        total += n
+    if cur:
+        batches.append(cur)
+    return batches

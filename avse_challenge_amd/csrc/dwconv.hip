@@ -45,6 +45,42 @@ __global__ __launch_bounds__(THREADS) void fwd_kernel(int C, int K, int dil, con
     }
 }
 
+// fwd_kernel for a ragged batch: row (b, c) has the extent L = len[b] (clamped into [0, K]) at row stride K; the input
+// reads as 0 at t >= L whatever it holds there, the output is 0 there.
+template <int P>
+__global__ __launch_bounds__(THREADS) void fwd_len_kernel(int C, int K, int dil, const float* __restrict__ x,
+                                                          const int32_t* __restrict__ lengths,
+                                                          const float* __restrict__ w, float* __restrict__ y) {
+    __shared__ float s[TILE + 2 * MAXHALO];
+    const int row = blockIdx.x, c = row % C;
+    const int L = min(max(lengths[row / C], 0), K);
+    const int halo = (P - 1) / 2 * dil;
+    const float* xr = x + (int64_t)row * K;
+    float* yr = y + (int64_t)row * K;
+    float wk[P];
+#pragma unroll
+    for (int k = 0; k < P; ++k) wk[k] = w[c * P + k];
+    for (int t0 = 0; t0 < L; t0 += TILE) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < TILE + 2 * halo; i += THREADS) {
+            const int t = t0 - halo + i;
+            s[i] = (t >= 0 && t < L) ? xr[t] : 0.f;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int p = 0; p < PER; ++p) {
+            const int i = threadIdx.x + p * THREADS, t = t0 + i;
+            if (t < L) {
+                float acc = 0.f;
+#pragma unroll
+                for (int k = 0; k < P; ++k) acc += wk[k] * s[i + k * dil];
+                yr[t] = acc;
+            }
+        }
+    }
+    for (int t = L + (int)threadIdx.x; t < K; t += THREADS) yr[t] = 0.f;
+}
+
 // dx[t] = sum_k w[k] dy[t - (k - h) * dil];  dw[k] += dy[t] * x[t + (k - h) * dil]
 // Streaming form, no LDS: thread t-loop over the row, BU elements per thread in flight; the taps' neighbours come
 // from the cache lines this workgroup just brought in (buffer loads: outside the row reads 0, no branches), so each
@@ -136,6 +172,26 @@ int avse_dwconv_fwd(int64_t B, int64_t C, int64_t K, int64_t P, int64_t dil, con
         case 5: hipLaunchKernelGGL(fwd_kernel<5>, grid, block, 0, st, (int)C, (int)K, (int)dil, x, w, y); break;
         default: hipLaunchKernelGGL(fwd_kernel<7>, grid, block, 0, st, (int)C, (int)K, (int)dil, x, w, y); break;
     }
+    AVSE_CHECK_LAUNCH();
+    return AVSE_OK;
+}
+
+int avse_dwconv_fwd_len(int64_t B, int64_t C, int64_t K, int64_t P, int64_t dil, const float* x, const int32_t* lengths,
+                        const float* w, float* y, avse_stream_t stream) {
+    if (!x || !lengths || !w || !y) return AVSE_EINVAL;
+    if (B <= 0 || C <= 0 || K <= 0 || K > (1LL << 29) || dil <= 0 || (P != 1 && P != 3 && P != 5 && P != 7) ||
+        (P - 1) / 2 * dil > MAXHALO || B * C > (1LL << 31) - 1)
+        return AVSE_ESHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    dim3 grid((unsigned)(B * C)), block(THREADS);
+#define L_(PP) hipLaunchKernelGGL(fwd_len_kernel<PP>, grid, block, 0, st, (int)C, (int)K, (int)dil, x, lengths, w, y)
+    switch ((int)P) {
+        case 1: L_(1); break;
+        case 3: L_(3); break;
+        case 5: L_(5); break;
+        default: L_(7); break;
+    }
+#undef L_
     AVSE_CHECK_LAUNCH();
     return AVSE_OK;
 }

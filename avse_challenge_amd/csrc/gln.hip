@@ -774,6 +774,199 @@ __global__ void dw_tail_kernel(const float* __restrict__ ws_dw, const float2* __
     }
 }
 
+
+// ----------------------------------------------------------------------------------------------------------
+// Length-aware forwards for ragged inference batches (avse_*_fwd_len): row (b, c) runs the dense kernel's loops with
+// the row extent L = len[b] (clamped into [0, K]) in place of K -- buffer range, loop bounds, statistics over C L --
+// while the row stride stays K, so its valid part and stats[b] equal the dense kernel on x[b:b+1, :, :L] bit for bit
+// (same per-thread element order).  Columns L .. K - 1 of the output are written as +0; what x holds there is never
+// used (the buffer range check returns 0).  L == 0: an all-zero sample, stats (0, 0).  Siblings of the dense kernels,
+// not template arguments of them: the dense instantiations keep their code and register figures.
+__device__ inline int row_len(const int32_t* __restrict__ lengths, int b, int K) { return min(max(lengths[b], 0), K); }
+
+__global__ __launch_bounds__(THREADS) void stats_len_kernel(int C, int K, const float* __restrict__ x,
+                                                            const int32_t* __restrict__ lengths,
+                                                            const float* __restrict__ alpha, float2* __restrict__ ws) {
+    __shared__ float red[4];
+    const int row = (int)blockIdx.x, b = row / C;
+    const int L = row_len(lengths, b, K);
+    if (L == 0) {
+        if (threadIdx.x == 0) ws[row] = make_float2(0.f, 0.f);
+        return;
+    }
+    const float a = alpha[0];
+    const float shift = prelu(x[(int64_t)b * C * K], a);
+    const auto rx = make_rsrc(x + (int64_t)row * K, L);
+    float s1 = 0.f, s2 = 0.f;
+    for (int t0 = 0; t0 < L; t0 += UB4 * V4 * THREADS) {
+        float4 xv[UB4];
+#pragma unroll
+        for (int j = 0; j < UB4; ++j) xv[j] = ld4(rx, t0 + (j * THREADS + (int)threadIdx.x) * V4);
+#pragma unroll
+        for (int j = 0; j < UB4; ++j) {
+            const int t = t0 + (j * THREADS + (int)threadIdx.x) * V4;
+#pragma unroll
+            for (int e = 0; e < V4; ++e) {
+                const float v = (t + e < L) ? prelu(f4at(xv[j], e), a) - shift : 0.f;
+                s1 += v;
+                s2 += v * v;
+            }
+        }
+    }
+    s1 = block_sum(s1, red);
+    s2 = block_sum(s2, red);
+    if (threadIdx.x == 0) ws[row] = make_float2(s1, s2);
+}
+
+template <bool QO = false>
+__global__ __launch_bounds__(THREADS) void apply_fused_len_kernel(int C, int K, const float* __restrict__ x,
+                                                                  const int32_t* __restrict__ lengths,
+                                                                  const float* __restrict__ alpha,
+                                                                  const float* __restrict__ gamma,
+                                                                  const float* __restrict__ beta,
+                                                                  const float2* __restrict__ ws, float eps,
+                                                                  float2* __restrict__ stats, float* __restrict__ y,
+                                                                  QOut q = QOut{}) {
+    __shared__ double red[8];
+    const int row = (int)blockIdx.x, b = row / C, c = row % C;
+    const int L = row_len(lengths, b, K);
+    const float a = alpha[0];
+    float2 st = make_float2(0.f, 0.f);
+    if (L > 0) st = sample_stats(sample_sums(ws, b, C, red), C, L, prelu(x[(int64_t)b * C * K], a), eps);
+    if (c == 0 && threadIdx.x == 0) stats[b] = st;
+    const float g = gamma[c] * st.y, o = beta[c] - gamma[c] * st.y * st.x;
+    const float* xr = x + (int64_t)row * K;
+    float* yr = QO ? nullptr : y + (int64_t)row * K;
+    const auto rx = make_rsrc(xr, L), ry = make_rsrc(QO ? xr : yr, L);
+    float sc = 1.f;
+    if constexpr (QO) sc = split_scale(*q.maxbits);
+    for (int t0 = 0; t0 < L; t0 += UB4 * V4 * THREADS) {
+        float4 xv[UB4];
+#pragma unroll
+        for (int jj = 0; jj < UB4; ++jj) xv[jj] = ld4(rx, t0 + (jj * THREADS + (int)threadIdx.x) * V4);
+#pragma unroll
+        for (int jj = 0; jj < UB4; ++jj) {
+            const int t = t0 + (jj * THREADS + (int)threadIdx.x) * V4;
+            float o4[4];
+#pragma unroll
+            for (int e = 0; e < V4; ++e) o4[e] = g * prelu(f4at(xv[jj], e), a) + o;
+            if constexpr (QO) {
+                if (t < L) q_store_quad(q, row, t, L, o4, sc);
+            } else {
+                st4_row(ry, yr, t, L, o4);
+            }
+        }
+    }
+    if constexpr (QO) {
+        q_zero_pad(q, row, L);                        // the planes' columns from L's last quadruple up to kp
+    } else {
+        for (int t = L + (int)threadIdx.x; t < K; t += THREADS) yr[t] = 0.f;
+    }
+}
+
+// q_bound_kernel per sample length; an empty sample bounds nothing
+__global__ __launch_bounds__(256) void q_bound_len_kernel(int C, int K, const float* __restrict__ x,
+                                                          const int32_t* __restrict__ lengths,
+                                                          const float* __restrict__ alpha,
+                                                          const float* __restrict__ gamma,
+                                                          const float* __restrict__ beta, const float2* __restrict__ ws,
+                                                          const float2* __restrict__ mm, float eps,
+                                                          uint32_t* __restrict__ maxbits) {
+    __shared__ double red[8];
+    __shared__ float fred[4];
+    const int b = blockIdx.x;
+    const int L = row_len(lengths, b, K);
+    if (L == 0) return;
+    const float a = alpha[0];
+    const float2 st = sample_stats(sample_sums(ws, b, C, red), C, L, prelu(x[(int64_t)b * C * K], a), eps);
+    float m = 0.f;
+    for (int c = threadIdx.x; c < C; c += 256) {
+        const float g = gamma[c] * st.y, o = beta[c] - gamma[c] * st.y * st.x;
+        const float2 e = mm[(int64_t)b * C + c];
+        m = fmaxf(m, fmaxf(fabsf(g * e.x + o), fabsf(g * e.y + o)));
+    }
+    for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    if ((threadIdx.x & 63) == 0) fred[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t v = __float_as_uint(fmaxf(fmaxf(fred[0], fred[1]), fmaxf(fred[2], fred[3])) * 1.0001f);
+        if (v) atomicMax(maxbits, v);
+    }
+}
+
+// dwconv_stats_kernel with the row extent len[b]: taps at t >= len[b] read 0; y1's columns past it are not written
+template <int P, bool MM = false>
+__global__ __launch_bounds__(THREADS) void dwconv_stats_len_kernel(int C, int K, int dil, const float* __restrict__ x,
+                                                                   const int32_t* __restrict__ lengths,
+                                                                   const float* __restrict__ w,
+                                                                   const float* __restrict__ alpha,
+                                                                   float* __restrict__ y1, float2* __restrict__ ws,
+                                                                   float2* __restrict__ mm = nullptr) {
+    __shared__ float red[4];
+    const int row = (int)blockIdx.x, b = row / C, c = row % C;
+    const int L = row_len(lengths, b, K);
+    if (L == 0) {
+        if (threadIdx.x == 0) {
+            ws[row] = make_float2(0.f, 0.f);
+            if constexpr (MM) mm[row] = make_float2(0.f, 0.f);
+        }
+        return;
+    }
+    const int halo = (P - 1) / 2 * dil;
+    const float a = alpha[0];
+    const float* xr = x + (int64_t)row * K;
+    float* yr = y1 + (int64_t)row * K;
+    float wk[P];
+#pragma unroll
+    for (int k = 0; k < P; ++k) wk[k] = w[c * P + k];
+    float y00 = 0.f;
+    {
+        const float* x0 = x + (int64_t)b * C * K;
+#pragma unroll
+        for (int k = 0; k < P; ++k) {
+            const int t = k * dil - halo;
+            y00 += w[k] * ((t >= 0 && t < L) ? x0[t] : 0.f);
+        }
+    }
+    const float shift = prelu(y00, a);
+    float s1 = 0.f, s2 = 0.f;
+    float pmin = __builtin_inff(), pmax = -__builtin_inff();
+    const auto rx = make_rsrc(xr, L);
+    for (int t0 = 0; t0 < L; t0 += DW_U * THREADS) {
+        float acc[DW_U];
+#pragma unroll
+        for (int j = 0; j < DW_U; ++j) {
+            const int t = t0 + j * THREADS + threadIdx.x;
+            acc[j] = 0.f;
+#pragma unroll
+            for (int k = 0; k < P; ++k) acc[j] += wk[k] * bufld<float>::ld(rx, t + k * dil - halo, 0);
+        }
+#pragma unroll
+        for (int j = 0; j < DW_U; ++j) {
+            const int t = t0 + j * THREADS + threadIdx.x;
+            if (t < L) {
+                yr[t] = acc[j];
+                const float pv = prelu(acc[j], a);
+                const float v = pv - shift;
+                s1 += v;
+                s2 += v * v;
+                if constexpr (MM) {
+                    pmin = fminf(pmin, pv);
+                    pmax = fmaxf(pmax, pv);
+                }
+            }
+        }
+    }
+    s1 = block_sum(s1, red);
+    s2 = block_sum(s2, red);
+    if (threadIdx.x == 0) ws[row] = make_float2(s1, s2);
+    if constexpr (MM) {
+        pmin = -block_sum_max(-pmin, red);
+        pmax = block_sum_max(pmax, red);
+        if (threadIdx.x == 0) mm[row] = make_float2(pmin, pmax);
+    }
+}
+
 }  // namespace gln
 }  // namespace avse
 
@@ -986,6 +1179,74 @@ int avse_dwconv_gln_bwd(int64_t B, int64_t C, int64_t K, int64_t P, int64_t dil,
     const int n = (int)(C * P + C);
     hipLaunchKernelGGL(dw_tail_kernel, dim3(1 + (n + 255) / 256), dim3(256), 0, st, ws_dw, (const float2*)ws, ws_a,
                        (int)B, (int)C, (int)P, dw, dgamma, dbeta, dalpha);
+    AVSE_CHECK_LAUNCH();
+    return AVSE_OK;
+}
+
+// ------------------------------------------------------------------ length-aware forwards (ragged inference batches)
+
+int avse_prelu_gln_fwd_len(int64_t B, int64_t C, int64_t K, const float* x, const int32_t* lengths, const float* alpha,
+                           const float* gamma, const float* beta, float eps, float* y, float* stats, float* workspace,
+                           avse_stream_t stream) {
+    if (!x || !lengths || !alpha || !gamma || !beta || !y || !stats || !workspace) return AVSE_EINVAL;
+    if (B <= 0 || C <= 0 || K <= 0 || B * C > (1LL << 31) - 1 || K > (1LL << 29)) return AVSE_ESHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    float2* ws = (float2*)workspace;
+    const unsigned rows = (unsigned)(B * C);
+    hipLaunchKernelGGL(stats_len_kernel, dim3(rows), dim3(THREADS), 0, st, (int)C, (int)K, x, lengths, alpha, ws);
+    AVSE_CHECK_LAUNCH();
+    hipLaunchKernelGGL(apply_fused_len_kernel<false>, dim3(rows), dim3(THREADS), 0, st, (int)C, (int)K, x, lengths, alpha,
+                       gamma, beta, (const float2*)ws, eps, (float2*)stats, y);
+    AVSE_CHECK_LAUNCH();
+    return AVSE_OK;
+}
+
+int avse_dwconv_gln_fwd_len(int64_t B, int64_t C, int64_t K, int64_t P, int64_t dil, const float* x,
+                            const int32_t* lengths, const float* w, const float* alpha, const float* gamma,
+                            const float* beta, float eps, float* y1, float* y, float* stats, float* workspace,
+                            avse_stream_t stream) {
+    if (!x || !lengths || !w || !alpha || !gamma || !beta || !y1 || !y || !stats || !workspace) return AVSE_EINVAL;
+    if (int rc = dw_check(B, C, K, P, dil)) return rc;
+    if (K > (1LL << 29)) return AVSE_ESHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    float2* ws = (float2*)workspace;
+    const unsigned rows = (unsigned)(B * C);
+#define L_(PP) hipLaunchKernelGGL(dwconv_stats_len_kernel<PP>, dim3(rows), dim3(THREADS), 0, st, (int)C, (int)K, (int)dil, \
+                              x, lengths, w, alpha, y1, ws)
+    AVSE_DW_P_SWITCH(P, L_)
+#undef L_
+    AVSE_CHECK_LAUNCH();
+    hipLaunchKernelGGL(apply_fused_len_kernel<false>, dim3(rows), dim3(THREADS), 0, st, (int)C, (int)K, y1, lengths, alpha,
+                       gamma, beta, (const float2*)ws, eps, (float2*)stats, y);
+    AVSE_CHECK_LAUNCH();
+    return AVSE_OK;
+}
+
+int avse_dwconv_gln_fwd_q_len(int64_t B, int64_t C, int64_t K, int64_t P, int64_t dil, const float* x,
+                              const int32_t* lengths, const float* w, const float* alpha, const float* gamma,
+                              const float* beta, float eps, float* y1, void* y_hi, void* y_lo, int64_t kp,
+                              uint32_t* y_maxbits, float* stats, float* workspace, avse_stream_t stream) {
+    if (!x || !lengths || !w || !alpha || !gamma || !beta || !y1 || !y_hi || !y_lo || !y_maxbits || !stats || !workspace)
+        return AVSE_EINVAL;
+    if (int rc = dw_check(B, C, K, P, dil)) return rc;
+    if (K > (1LL << 29) || kp < K || kp % 8 || B * C * kp >= (1LL << 40)) return AVSE_ESHAPE;
+    if (((uintptr_t)y_hi | (uintptr_t)y_lo) % 16) return AVSE_EALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    float2* ws = (float2*)workspace;
+    float2* mm = ws + B * C;
+    const unsigned rows = (unsigned)(B * C);
+    if (hipMemsetAsync(y_maxbits, 0, 4, st) != hipSuccess) return AVSE_ELAUNCH;
+#define L_(PP) hipLaunchKernelGGL((dwconv_stats_len_kernel<PP, true>), dim3(rows), dim3(THREADS), 0, st, (int)C, (int)K, \
+                              (int)dil, x, lengths, w, alpha, y1, ws, mm)
+    AVSE_DW_P_SWITCH(P, L_)
+#undef L_
+    AVSE_CHECK_LAUNCH();
+    hipLaunchKernelGGL(q_bound_len_kernel, dim3((unsigned)B), dim3(256), 0, st, (int)C, (int)K, y1, lengths, alpha, gamma,
+                       beta, (const float2*)ws, (const float2*)mm, eps, y_maxbits);
+    AVSE_CHECK_LAUNCH();
+    hipLaunchKernelGGL(apply_fused_len_kernel<true>, dim3(rows), dim3(THREADS), 0, st, (int)C, (int)K, y1, lengths, alpha,
+                       gamma, beta, (const float2*)ws, eps, (float2*)stats, nullptr,
+                       QOut{y_maxbits, (_Float16*)y_hi, (_Float16*)y_lo, (int)kp});
     AVSE_CHECK_LAUNCH();
     return AVSE_OK;
 }

@@ -1367,10 +1367,64 @@ def bnact_pool_frames_bwd(x, g, idx, stats, gamma, beta, act, alpha, training):
     return dx, dgamma, dbeta, dalpha
 
 
+# ------------------------------------------------------------------------ ragged batches (avse4 inference)
+
+class Lengths:
+    """Per-sample extents of a zero-padded ragged batch: the host values (validated without a device sync) and their
+    int32 device copy, made once and handed to every length-aware launch of a forward."""
+
+    def __init__(self, lengths, device):
+        host = lengths.tolist() if hasattr(lengths, "tolist") else list(lengths)
+        if not host or any(int(v) != v for v in host):
+            raise ValueError(f"lengths must be a non-empty sequence of integers, got {host}")
+        self.host = tuple(int(v) for v in host)
+        if min(self.host) < -2 ** 31 or max(self.host) >= 2 ** 31:
+            raise ValueError("lengths must fit int32")
+        self.dev = torch.tensor(self.host, dtype=torch.int32, device=device)
+
+    def checked(self, batch, extent, what):
+        """self after the host check 1 <= len <= extent for each of `batch` samples (ValueError otherwise)."""
+        if len(self.host) != batch:
+            raise ValueError(f"{what}: {len(self.host)} lengths for a batch of {batch}")
+        if min(self.host) < 1 or max(self.host) > extent:
+            raise ValueError(f"{what}: lengths must lie in [1, {extent}], got [{min(self.host)}, {max(self.host)}]")
+        return self
+
+
+def _lengths(lengths, batch, extent, device, what):
+    if not isinstance(lengths, Lengths):
+        lengths = Lengths(lengths, device)
+    elif lengths.dev.device != device:
+        raise ValueError(f"{what}: lengths live on {lengths.dev.device}, the tensors on {device}")
+    return lengths.checked(batch, extent, what)
+
+
+def upsample_linear_len(v, vis_lengths, lengths, up, out):
+    """out[b, :, :lengths[b]] = F.interpolate(v[b, :, :vis_lengths[b]], scale_factor=up, mode="linear") padded with 0 or
+    cropped to lengths[b] columns, 0 from there on (avse_upsample_linear_len).  v (B, C, Tv), out (B, C, K): fp32, unit
+    stride along time; out may be a channel slice of a wider tensor.  Returns out."""
+    if v.dim() != 3 or out.dim() != 3 or v.shape[:2] != out.shape[:2]:
+        raise ValueError(f"upsample_linear_len: v {tuple(v.shape)} and out {tuple(out.shape)} must be (B, C, *)")
+    Bn, C, Tv = v.shape
+    Kn = out.shape[2]
+    vl = _lengths(vis_lengths, Bn, Tv, v.device, "upsample_linear_len (vis_lengths)")
+    kl = _lengths(lengths, Bn, Kn, v.device, "upsample_linear_len (lengths)")
+    _need_gpu(v, out)
+    if v.dtype != torch.float32 or out.dtype != torch.float32 or v.stride(2) != 1 or out.stride(2) != 1:
+        raise ValueError("upsample_linear_len: fp32 tensors with unit stride along time")
+    check(_lib.lib().avse_upsample_linear_len(Bn, C, Tv, Kn, int(up), ptr(v), v.stride(0), v.stride(1), ptr(vl.dev),
+                                              ptr(kl.dev), ptr(out), out.stride(0), out.stride(1),
+                                              stream_ptr(v.device)), "avse_upsample_linear_len")
+    return out
+
+
 # ------------------------------------------------------------------------ PReLU -> gLN (avse4)
 
-def prelu_gln_fwd(x, alpha, gamma, beta, eps=1e-8):
-    """gLN(PReLU(x)) on (B, C, K); returns (y, stats (B, 2) = mean, rstd)."""
+def prelu_gln_fwd(x, alpha, gamma, beta, eps=1e-8, lengths=None):
+    """gLN(PReLU(x)) on (B, C, K); returns (y, stats (B, 2) = mean, rstd).  lengths (a sequence or a Lengths, inference
+    only): sample b is normalised over its first lengths[b] columns alone and y is 0 past them (avse_prelu_gln_fwd_len)."""
+    if lengths is not None:
+        lengths = _lengths(lengths, x.shape[0], x.shape[2], x.device, "prelu_gln_fwd")
     _need_gpu(x, alpha, gamma, beta)
     x = x.float().contiguous()
     Bn, C, Kn = x.shape
@@ -1378,6 +1432,11 @@ def prelu_gln_fwd(x, alpha, gamma, beta, eps=1e-8):
     stats = torch.empty((Bn, 2), device=x.device, dtype=torch.float32)
     L = _lib.lib()
     ws = torch.empty((L.avse_prelu_gln_workspace_bytes(Bn, C) + 3) // 4, device=x.device, dtype=torch.float32)
+    if lengths is not None:
+        check(L.avse_prelu_gln_fwd_len(Bn, C, Kn, ptr(x), ptr(lengths.dev), ptr(alpha.float().contiguous()),
+                                       ptr(gamma.float().contiguous()), ptr(beta.float().contiguous()), float(eps),
+                                       ptr(y), ptr(stats), ptr(ws), stream_ptr(x.device)), "avse_prelu_gln_fwd_len")
+        return y, stats
     tap = _tap_begin("avse_prelu_gln_fwd", x.device)
     check(L.avse_prelu_gln_fwd(Bn, C, Kn, ptr(x), ptr(alpha.float().contiguous()), ptr(gamma.float().contiguous()),
                                ptr(beta.float().contiguous()), float(eps), ptr(y), ptr(stats), ptr(ws),
@@ -1416,12 +1475,20 @@ def prelu_gln_bwd(x, alpha, gamma, stats, dy, planes=False):
 
 # ------------------------------------------------------------------------ depthwise dilated conv1d
 
-def dwconv_fwd(x, w, dilation):
+def dwconv_fwd(x, w, dilation, lengths=None):
+    """Depthwise 'same' conv1d.  lengths (inference only): x reads as 0 past lengths[b] whatever it holds there and y
+    is 0 there (avse_dwconv_fwd_len)."""
+    if lengths is not None:
+        lengths = _lengths(lengths, x.shape[0], x.shape[2], x.device, "dwconv_fwd")
     _need_gpu(x, w)
     x = x.float().contiguous()
     Bn, C, Kn = x.shape
     w2 = w.reshape(C, -1).float().contiguous()
     y = torch.empty_like(x)
+    if lengths is not None:
+        check(_lib.lib().avse_dwconv_fwd_len(Bn, C, Kn, w2.shape[1], int(dilation), ptr(x), ptr(lengths.dev), ptr(w2),
+                                             ptr(y), stream_ptr(x.device)), "avse_dwconv_fwd_len")
+        return y
     check(_lib.lib().avse_dwconv_fwd(Bn, C, Kn, w2.shape[1], int(dilation), ptr(x), ptr(w2), ptr(y),
                                      stream_ptr(x.device)), "avse_dwconv_fwd")
     return y
@@ -1470,10 +1537,13 @@ def _planes_carrier(shape, device):
     return carrier, sp, cp
 
 
-def dwconv_gln_fwd(x, w, dilation, alpha, gamma, beta, eps=1e-8, planes=False):
+def dwconv_gln_fwd(x, w, dilation, alpha, gamma, beta, eps=1e-8, planes=False, lengths=None):
     """y1 = depthwise dilated conv1d(x) (w (C, 1, P)), y = gLN(PReLU(y1)); returns (y, y1, stats (B, 2)).  planes: y is
     written only as the split-fp16 planes of its consumer GEMM (avse_dwconv_gln_fwd_q) and returned as their carrier
-    (PLANES_ATTR)."""
+    (PLANES_ATTR).  lengths (inference only): sample b is its first lengths[b] columns alone, y (or the planes) is 0
+    past them and y1 is not written there (avse_dwconv_gln_fwd_len / _q_len)."""
+    if lengths is not None:
+        lengths = _lengths(lengths, x.shape[0], x.shape[2], x.device, "dwconv_gln_fwd")
     _need_gpu(x, w, alpha, gamma, beta)
     x = x.float().contiguous()
     Bn, C, Kn = x.shape
@@ -1482,6 +1552,19 @@ def dwconv_gln_fwd(x, w, dilation, alpha, gamma, beta, eps=1e-8, planes=False):
     L = _lib.lib()
     ws = torch.empty((L.avse_dwconv_gln_workspace_bytes(Bn, C) + 3) // 4, device=x.device, dtype=torch.float32)
     y1 = torch.empty_like(x)
+    if lengths is not None:
+        pars = (ptr(alpha.float().contiguous()), ptr(gamma.float().contiguous()), ptr(beta.float().contiguous()))
+        if planes:
+            y, sp, cp = _planes_carrier((Bn, C, Kn), x.device)
+            check(L.avse_dwconv_gln_fwd_q_len(Bn, C, Kn, w2.shape[1], int(dilation), ptr(x), ptr(lengths.dev), ptr(w2),
+                                              *pars, float(eps), ptr(y1), ptr(sp.hi), ptr(sp.lo), cp, ptr(sp.mb),
+                                              ptr(stats), ptr(ws), stream_ptr(x.device)), "avse_dwconv_gln_fwd_q_len")
+        else:
+            y = torch.empty_like(x)
+            check(L.avse_dwconv_gln_fwd_len(Bn, C, Kn, w2.shape[1], int(dilation), ptr(x), ptr(lengths.dev), ptr(w2),
+                                            *pars, float(eps), ptr(y1), ptr(y), ptr(stats), ptr(ws),
+                                            stream_ptr(x.device)), "avse_dwconv_gln_fwd_len")
+        return y, y1, stats
     if planes:
         y, sp, cp = _planes_carrier((Bn, C, Kn), x.device)
         tap = _tap_begin("avse_dwconv_gln_fwd_q", x.device)

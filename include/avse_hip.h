@@ -471,6 +471,36 @@ int avse_dwconv_gln_bwd(int64_t B, int64_t C, int64_t K, int64_t P, int64_t dil,
                         float* dx, float* dw, float* dalpha, float* dgamma, float* dbeta, float* workspace,
                         avse_stream_t stream);
 
+/* ---------------------------------------------------------------- ragged inference batches (avse4) ----
+ * Forwards for a zero-padded batch of utterances of different lengths: lengths (device, B x int32) is each sample's
+ * extent along K.  Row (b, c) runs the dense forward's loops with len[b] (clamped into [0, K]) in place of K at row
+ * stride K, so the valid part of y and stats[b] equal the dense call on the contiguous slice x[b:b+1, :, :len[b]] bit
+ * for bit; what x holds at columns >= len[b] is never used (it reads as 0: NaN / Inf there do not propagate), and
+ * y (or the planes, up to kp) is written as +0 there.  y1's columns past len[b] are not written.  len[b] == 0 gives
+ * an all-zero sample with stats (0, 0).  Inference only: there is no backward.  Workspaces as the dense calls. */
+int avse_prelu_gln_fwd_len(int64_t B, int64_t C, int64_t K, const float* x, const int32_t* lengths, const float* alpha,
+                           const float* gamma, const float* beta, float eps, float* y, float* stats, float* workspace,
+                           avse_stream_t stream);
+int avse_dwconv_gln_fwd_len(int64_t B, int64_t C, int64_t K, int64_t P, int64_t dil, const float* x,
+                            const int32_t* lengths, const float* w, const float* alpha, const float* gamma,
+                            const float* beta, float eps, float* y1, float* y, float* stats, float* workspace,
+                            avse_stream_t stream);
+/* y as the split-fp16 planes (as avse_dwconv_gln_fwd_q); *y_maxbits bounds max |y| over the valid parts of all samples */
+int avse_dwconv_gln_fwd_q_len(int64_t B, int64_t C, int64_t K, int64_t P, int64_t dil, const float* x,
+                              const int32_t* lengths, const float* w, const float* alpha, const float* gamma,
+                              const float* beta, float eps, float* y1, void* y_hi, void* y_lo, int64_t kp,
+                              uint32_t* y_maxbits, float* stats, float* workspace, avse_stream_t stream);
+/* avse_dwconv_fwd with the same length semantics (VisualConv1D over video frames, model.py:191-198) */
+int avse_dwconv_fwd_len(int64_t B, int64_t C, int64_t K, int64_t P, int64_t dil, const float* x, const int32_t* lengths,
+                        const float* w, float* y, avse_stream_t stream);
+/* Per sample linear upsampling by `up` of v (B, C, n_in_max), valid frames vlen[b], to klen[b] columns of out
+ * (B, C, K): F.interpolate(v[b, :, :vlen[b]], scale_factor=up, mode="linear") padded with 0 / cropped to klen[b]
+ * (model.py:166-176), 0 from there to K.  v / out: element strides of the batch and channel axes (unit stride along
+ * time), so out may be a channel slice of a wider tensor. */
+int avse_upsample_linear_len(int64_t B, int64_t C, int64_t n_in_max, int64_t K, int64_t up, const float* v, int64_t v_bs,
+                             int64_t v_cs, const int32_t* vlen, const int32_t* klen, float* out, int64_t out_bs,
+                             int64_t out_cs, avse_stream_t stream);
+
 /* ---------------------------------------------------------------- LSTM recurrence ----------
  * Replaces the per-step cuDNN/MIOpen LSTM behind nn.LSTM at baseline/avse1/model.py:88 (FusionNet:
  * LSTM(1540 -> 257), batch_first) and baseline/avse2/model.py:101-102 (DPRNN, bidirectional: one call per
