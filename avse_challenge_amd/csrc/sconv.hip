@@ -411,6 +411,8 @@ __global__ __launch_bounds__(512, 1) void dgrad2_kernel(DArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------ weight gradient
+// Two kernels: wgrad9_kernel (below; stride 1 where the stage fits, i.e. every trunk shape) and the per-row kernel
+// (stride 2, and stride-1 rows too wide for wgrad9_kernel's stage).
 // Per kernel row kh: dW[o][i][kh][kw] for the 3 kw taps, a GEMM with M = o, N = i and the reduction over output pixels.
 // Workgroup (pixel-chunk range, o block of OB = 64 or 128, i block of 64, kh): OB / 32 x 2 waves of 32 x 32 (o, i)
 // blocks x 3 taps (48 accumulators).  Per 64-pixel raster chunk: the dY rows (64 pixels x the o block) and the input
@@ -642,6 +644,207 @@ __global__ __launch_bounds__(512, 1) void wgrad_kernel(WArgs a) {
                 }
 }
 
+// Stride 1, all 9 taps in one workgroup: workgroup (pixel-chunk range, o block of OB, i block of 64), wave = 32 o x 32 i
+// x 9 taps (144 accumulators).  OB = 128: the 8 waves are the 4 x 2 blocks, one slab per range; OB = 64: 2 x 2 blocks x
+// KG = 2 k-step groups.  Per 64-pixel chunk the dY rows are staged once and the input rows of the flat (n, h) raster
+// once, from one row above the chunk's first output row g0 to one row below its last: staged row t is flat input row
+// g0 - 1 + t (stride 1: the input and output rasters are the same), a segment of RS = Wo + 2 positions, zeros (OOB) for
+// rows outside the tensor and the halo columns.  Output pixel (staged output row dr, column wo) reads position
+// (dr + kh) RS + wo + kw for tap (kh, kw).  Frame edges: a chunk may span several frames, so the staged row above a
+// frame's first output row (below its last) holds the neighbouring frame's pixels; the kh = 0 (kh = 2) fragment rows of
+// such a pixel are redirected, per lane, to a row of zeros that the kernel writes itself before its first barrier (LDS is
+// never assumed clean).  Per chunk and wave: 4 / KG k-steps x 9 taps x 3 products = 108 / KG MFMAs behind one barrier.
+constexpr int ZROWB = 256;                      // the zero row: one staged position
+
+template <int OB>
+__global__ __launch_bounds__(512, 1) void wgrad9_kernel(WArgs a) {
+    constexpr int BW = OB / 16, KG = 8 / BW, WAVES = 8, YRB = OB * 4, KS = (WG_CHUNK / 16) / KG;
+    constexpr int YIMG = WG_CHUNK * YRB, STG = YIMG + NPW_MAX * XROWB;
+    constexpr int PY = YIMG / 1024, YPP = 1024 / YRB;
+    constexpr int MP = (PY + NPW_MAX / 4 + WAVES - 1) / WAVES;
+    constexpr int ZOFF = 2 * STG;
+    __shared__ __attribute__((aligned(1024))) uint8_t lds[2 * STG + ZROWB];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);            // the o / i blocks of one range run on one XCD
+    int t = bid;
+    const int ib = t % a.nib;
+    t /= a.nib;
+    const int ob = t % a.nob;
+    const int r = t / a.nob;
+    const int c_lo = (int)((int64_t)r * a.chunks / a.ranges), c_hi = (int)((int64_t)(r + 1) * a.chunks / a.ranges);
+    const int NHWo = a.N * a.Ho * a.Wo, NHo = a.N * a.Ho;
+    const i4_t rx = dma_rsrc(a.xq, (int64_t)NHWo * a.Ci * 4);
+    const i4_t ry = dma_rsrc(a.dyq, (int64_t)NHWo * a.Co * 4);
+    const uint32_t lds0 = lds_u32(lds);
+    const int PT = PY + a.npw / 4;
+    const int npieces = (PT - wave + WAVES - 1) / WAVES;
+    const uint32_t xpixb = (uint32_t)a.Ci * 4u, ypixb = (uint32_t)a.Co * 4u;
+    const int ypr = lane / (YRB / 16), ypc = lane % (YRB / 16);
+    const int xpr = lane >> 4, xpc = lane & 15;
+
+    if (threadIdx.x < ZROWB / 4) reinterpret_cast<uint32_t*>(lds + ZOFF)[threadIdx.x] = 0u;
+
+    // per DMA piece of this wave, everything that does not depend on the chunk (as in wgrad_kernel); X pieces: the
+    // staged row t of the position and the byte offset of its input column within an input row
+    int pj[MP];
+    uint32_t poff[MP];
+#pragma unroll
+    for (int m = 0; m < MP; ++m) {
+        const int k = wave + WAVES * m;
+        if (k < PY) {
+            const int j = YPP * k + ypr;
+            pj[m] = j;
+            poff[m] = (uint32_t)j * ypixb + (uint32_t)(ob * YRB) + 16u * tswz(j, ypc);
+        } else {
+            const int q = 4 * (k - PY) + xpr;
+            const int rk = q / a.RS, wi = q - rk * a.RS - 1;
+            const bool ok = q < a.npw && wi >= 0 && wi < a.Wi;
+            pj[m] = rk;
+            poff[m] = ok ? (uint32_t)wi * xpixb + (uint32_t)(ib * XROWB) + 16u * tswz(q, xpc) : OOB;
+        }
+    }
+    const uint32_t xrowb = (uint32_t)a.Wi * xpixb;
+    struct Cur {
+        int g0, w0;
+    };
+    auto cur_at = [&](int c) {
+        Cur cu;
+        const int p0 = c * WG_CHUNK;
+        cu.g0 = p0 / a.Wo;
+        cu.w0 = p0 - cu.g0 * a.Wo;
+        return cu;
+    };
+    auto cur_next = [&](Cur& cu) {
+        cu.w0 += a.r64;
+        cu.g0 += a.q64;
+        if (cu.w0 >= a.Wo) {
+            cu.w0 -= a.Wo;
+            ++cu.g0;
+        }
+    };
+    auto issue = [&](int c, const Cur& cu, int buf) {
+        const int p0 = c * WG_CHUNK;
+        const uint32_t ybase = (uint32_t)p0 * ypixb;
+        const uint32_t img = lds0 + buf * STG;
+#pragma unroll
+        for (int m = 0; m < MP; ++m) {
+            if (m >= npieces) break;
+            const int k = wave + WAVES * m;
+            if (k < PY) {                                        // dY rows: chunk pixel pj
+                dma16(ry, img + k * 1024, p0 + pj[m] < NHWo ? ybase + poff[m] : OOB);
+            } else {                                             // staged row pj = flat input row g0 - 1 + pj
+                const int gi = cu.g0 - 1 + pj[m];
+                const bool ok = poff[m] != OOB && gi >= 0 && gi < NHo;
+                dma16(rx, img + YIMG + (k - PY) * 1024, ok ? (uint32_t)gi * xrowb + poff[m] : OOB);
+            }
+        }
+    };
+
+    const int kg = wave / BW, lw = wave % BW;
+    const int obw = lw >> 1, ibw = lw & 1;                       // this wave's 32 o x 32 i
+    floatx16 acc[3][3];
+#pragma unroll
+    for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+        for (int kw = 0; kw < 3; ++kw)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[kh][kw][e] = 0.f;
+
+    const int g = lane >> 4, li = lane & 15;
+    // the lane's bytes of a staged input position (plane hi; lo 32 B on): chunk 2 ibw + (g & 1), 8 B per 4 lanes
+    const int xbyte = (2 * ibw + (g & 1)) * 64 + 8 * (li & 3);
+    Cur ci_ = cur_at(c_lo), cc_ = ci_;
+    if (c_lo < c_hi) {
+        issue(c_lo, ci_, 0);
+        cur_next(ci_);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");            // the zero row is written before the first barrier
+    for (int c = c_lo; c < c_hi; ++c) {
+        const int it = c - c_lo;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        if (c + 1 < c_hi) {
+            issue(c + 1, ci_, (it + 1) & 1);
+            cur_next(ci_);
+        }
+        const uint8_t* yimg = lds + (it & 1) * STG;
+        const int xoff = (it & 1) * STG + YIMG;
+        const int w0 = cc_.w0;
+        int n0, ho0;
+        divmod_small(cc_.g0, a.Ho, a.inv_ho, n0, ho0);
+#pragma unroll
+        for (int s2 = 0; s2 < KS; ++s2) {
+            const int s = kg * KS + s2;
+            int ry_[2], pos0[2];
+            bool top[2], bot[2];
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int j = 16 * s + 8 * (g >> 1) + (li >> 2) + 4 * u;       // the lane's pixel of the k-step
+                int dr, wo, dn, ho;
+                divmod_small(w0 + j, a.Wo, a.inv_wo, dr, wo);
+                divmod_small(ho0 + dr, a.Ho, a.inv_ho, dn, ho);
+                ry_[u] = j;
+                pos0[u] = dr * a.RS + wo;
+                top[u] = ho == 0;
+                bot[u] = ho == a.Ho - 1;
+            }
+            const half8 ah = tfrag<YRB>(yimg, ry_, obw, 0, lane);
+            const half8 al = tfrag<YRB>(yimg, ry_, obw, 1, lane);
+#pragma unroll
+            for (int kh = 0; kh < 3; ++kh) {
+                half8 bh[3], bl[3];
+#pragma unroll
+                for (int kw = 0; kw < 3; ++kw) {
+                    s4_t vh[2], vl[2];
+#pragma unroll
+                    for (int u = 0; u < 2; ++u) {
+                        const int pos = pos0[u] + kh * a.RS + kw;
+                        const bool edge = (kh == 0 && top[u]) || (kh == 2 && bot[u]);
+                        const int off = edge ? ZOFF + xbyte : xoff + pos * XROWB + (xbyte ^ ((pos & 3) << 6));
+                        vh[u] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(lds + off));
+                        vl[u] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(lds + off + 32));
+                    }
+                    typedef short s8_t __attribute__((ext_vector_type(8)));
+                    const s8_t wh = {vh[0][0], vh[0][1], vh[0][2], vh[0][3], vh[1][0], vh[1][1], vh[1][2], vh[1][3]};
+                    const s8_t wl = {vl[0][0], vl[0][1], vl[0][2], vl[0][3], vl[1][0], vl[1][1], vl[1][2], vl[1][3]};
+                    bh[kw] = __builtin_bit_cast(half8, wh);
+                    bl[kw] = __builtin_bit_cast(half8, wl);
+                }
+                // product-major over the kernel row's 3 independent accumulators
+#pragma unroll
+                for (int kw = 0; kw < 3; ++kw)
+                    acc[kh][kw] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[kw], acc[kh][kw], 0, 0, 0);
+#pragma unroll
+                for (int kw = 0; kw < 3; ++kw)
+                    acc[kh][kw] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl[kw], acc[kh][kw], 0, 0, 0);
+#pragma unroll
+                for (int kw = 0; kw < 3; ++kw)
+                    acc[kh][kw] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[kw], acc[kh][kw], 0, 0, 0);
+            }
+        }
+        cur_next(cc_);
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    }
+    // partial tiles: acc[kh][kw] register 4 q + e = row o = OB ob + 32 obw + 8 q + 4 (lane >> 5) + e, column
+    // i = 64 ib + 32 ibw + (lane & 31)
+    const float sc = split_unscale(1.f, *a.xmax, *a.dymax);
+    float* pp = a.part + (int64_t)(r * KG + kg) * 9 * a.Co * a.Ci;
+#pragma unroll
+    for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+        for (int kw = 0; kw < 3; ++kw)
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int o = OB * ob + 32 * obw + 8 * q + 4 * (lane >> 5) + e;
+                    const int i = 64 * ib + 32 * ibw + (lane & 31);
+                    pp[((int64_t)(kh * 3 + kw) * a.Co + o) * a.Ci + i] = acc[kh][kw][4 * q + e] * sc;
+                }
+}
+
 // dW[o][i][kh][kw] = sum over ranges of part[range][kh][kw][o][i]: workgroup = 64 consecutive elements x 4 range
 // slices (coalesced 256-B reads per slice and range), the slices combined in a fixed order (deterministic)
 __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ part, int ranges, int Co, int Ci,
@@ -725,6 +928,16 @@ inline int wg_npw(int Wo, int RS) {
 }
 inline int wg_ranges(int chunks, int blocks_per_range) {
     return std::max(1, std::min(chunks, (512 + blocks_per_range - 1) / blocks_per_range));
+}
+// the 9-tap kernel: the chunk's output rows and one input row above and below
+inline int wg9_npw(int Wo, int RS) {
+    const int rows = (WG_CHUNK - 1 + Wo - 1) / Wo + 1;
+    return ((rows + 2) * RS + 3) / 4 * 4;
+}
+// ... one workgroup per CU (256): a range's nob x nib blocks stay on one XCD, and the partial slabs (75 MB for the
+// trunk shapes) stay below the per-row plan's
+inline int wg9_ranges(int chunks, int blocks_per_range) {
+    return std::max(1, std::min(chunks, (256 + blocks_per_range - 1) / blocks_per_range));
 }
 
 }  // namespace scv
@@ -899,7 +1112,7 @@ static int sconv_launch(int64_t N, int64_t Hi, int64_t Wi, int64_t ci, int64_t c
     return AVSE_OK;
 }
 
-static int wg_setup(int64_t N, int64_t Hi, int64_t Wi, int64_t ci, int64_t co, int64_t stride, WArgs& a) {
+static int wg_setup(int64_t N, int64_t Hi, int64_t Wi, int64_t ci, int64_t co, int64_t stride, WArgs& a, bool& rows9) {
     if (N <= 0 || Hi <= 0 || Wi <= 0 || ci <= 0 || co <= 0 || ci % 64 || co % 64 || (stride != 1 && stride != 2))
         return AVSE_ESHAPE;
     if (N * Hi * Wi * ci * 4 >= (1LL << 31) - 4096) return AVSE_ESHAPE;
@@ -911,14 +1124,17 @@ static int wg_setup(int64_t N, int64_t Hi, int64_t Wi, int64_t ci, int64_t co, i
     a.Ho = out_dim((int)Hi, (int)stride);
     a.Wo = out_dim((int)Wi, (int)stride);
     a.RS = (int)stride * a.Wo + 2;
-    a.npw = wg_npw(a.Wo, a.RS);
+    // stride 1: the 9-tap kernel when its stage (2 rows more than one kernel row's) fits, which every trunk shape's
+    // does (Wo <= 28, and 30 .. 34); wider rows and stride 2 (a 116-130 KB merged stage) take the per-row kernel
+    rows9 = stride == 1 && wg9_npw(a.Wo, a.RS) <= NPW_MAX;
+    a.npw = rows9 ? wg9_npw(a.Wo, a.RS) : wg_npw(a.Wo, a.RS);
     if (a.npw > NPW_MAX) return AVSE_ESHAPE;
     const int64_t NHWo = N * a.Ho * a.Wo;
     if (NHWo * co * 4 >= (1LL << 31) - 4096) return AVSE_ESHAPE;
     a.chunks = (int)((NHWo + WG_CHUNK - 1) / WG_CHUNK);
     a.nob = (int)(co % 128 ? co / 64 : co / 128);               // o blocks of OB = 128 when they tile co, else 64
     a.nib = (int)(ci / 64);
-    a.ranges = wg_ranges(a.chunks, 3 * a.nob * a.nib);
+    a.ranges = rows9 ? wg9_ranges(a.chunks, a.nob * a.nib) : wg_ranges(a.chunks, 3 * a.nob * a.nib);
     a.inv_ho = 1.f / (float)a.Ho;
     a.inv_wo = 1.f / (float)a.Wo;
     a.q64 = WG_CHUNK / a.Wo;
@@ -926,13 +1142,15 @@ static int wg_setup(int64_t N, int64_t Hi, int64_t Wi, int64_t ci, int64_t co, i
     return AVSE_OK;
 }
 
-// k-step groups of the weight-gradient kernel (partial slabs per range): 8 / (OB / 32)
-static int wg_kg(int64_t co) { return co % 128 ? 4 : 2; }
+// k-step groups of the weight-gradient kernels (partial slabs per range): the per-row kernel's 8 / (OB / 32), the
+// 9-tap kernel's 8 / (OB / 16)
+static int wg_kg(int64_t co, bool rows9) { return rows9 ? (co % 128 ? 2 : 1) : (co % 128 ? 4 : 2); }
 
 int64_t avse_sconv_wgrad_workspace_bytes(int64_t N, int64_t Hi, int64_t Wi, int64_t ci, int64_t co, int64_t stride) {
     WArgs a;
-    if (wg_setup(N, Hi, Wi, ci, co, stride, a) != AVSE_OK) return -1;
-    return (int64_t)a.ranges * wg_kg(co) * 9 * co * ci * 4;               // KG partial slabs per range
+    bool rows9;
+    if (wg_setup(N, Hi, Wi, ci, co, stride, a, rows9) != AVSE_OK) return -1;
+    return (int64_t)a.ranges * wg_kg(co, rows9) * 9 * co * ci * 4;        // KG partial slabs per range
 }
 
 int avse_sconv_wgrad(int64_t N, int64_t Hi, int64_t Wi, int64_t ci, int64_t co, int64_t stride, const void* xq,
@@ -940,7 +1158,8 @@ int avse_sconv_wgrad(int64_t N, int64_t Hi, int64_t Wi, int64_t ci, int64_t co, 
                      avse_stream_t stream) {
     if (!xq || !xmax || !dyq || !dymax || !dw || !workspace) return AVSE_EINVAL;
     WArgs a;
-    const int rc = wg_setup(N, Hi, Wi, ci, co, stride, a);
+    bool rows9;
+    const int rc = wg_setup(N, Hi, Wi, ci, co, stride, a, rows9);
     if (rc != AVSE_OK) return rc;
     a.xq = xq;
     a.dyq = dyq;
@@ -948,9 +1167,12 @@ int avse_sconv_wgrad(int64_t N, int64_t Hi, int64_t Wi, int64_t ci, int64_t co, 
     a.dymax = dymax;
     a.part = workspace;
     const bool ob128 = co % 128 == 0;
-    const dim3 grid((unsigned)(a.ranges * 3 * a.nob * a.nib)), block(512);
+    const dim3 grid((unsigned)(a.ranges * (rows9 ? 1 : 3) * a.nob * a.nib)), block(512);
     hipStream_t st = (hipStream_t)stream;
-    if (ob128) {
+    if (rows9) {
+        if (ob128) hipLaunchKernelGGL((wgrad9_kernel<128>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((wgrad9_kernel<64>), grid, block, 0, st, a);
+    } else if (ob128) {
         if (stride == 1) hipLaunchKernelGGL((wgrad_kernel<1, 128>), grid, block, 0, st, a);
         else hipLaunchKernelGGL((wgrad_kernel<2, 128>), grid, block, 0, st, a);
     } else {
@@ -960,7 +1182,7 @@ int avse_sconv_wgrad(int64_t N, int64_t Hi, int64_t Wi, int64_t ci, int64_t co, 
     AVSE_CHECK_LAUNCH();
     const int64_t total = 9 * co * ci;
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((total + 63) / 64)), dim3(256), 0, st, a.part,
-                       a.ranges * wg_kg(co), (int)co, (int)ci, dw);
+                       a.ranges * wg_kg(co, rows9), (int)co, (int)ci, dw);
     AVSE_CHECK_LAUNCH();
     return AVSE_OK;
 }

@@ -626,7 +626,9 @@ int avse_dconv_wprep2(const float* w, void* wq, void* wq_t, uint32_t* maxbits, u
  *     swapped); transposed = 2 the stride-2 input gradient's phase images (avse_sconv_dgrad2);
  *   avse_sconv_fwd: y (N, Ho, Wo, co) fp32, Ho = (Hi - 1) / stride + 1;
  *   avse_sconv_wgrad: dW (co, ci, 3, 3) from the split input (N, Hi, Wi, ci) and output gradient (N, Ho, Wo, co);
- *     workspace of avse_sconv_wgrad_workspace_bytes (< 0: shape not supported);
+ *     workspace of avse_sconv_wgrad_workspace_bytes (< 0: shape not supported): the kernel's partial slabs, summed in
+ *     a fixed order (no atomics).  Stride 1 with rows of up to 28 pixels (30 .. 34 too): one workgroup covers all 9
+ *     taps of its (o, i) block; stride 2 and wider rows: one workgroup per kernel row;
  *   avse_sconv_dgrad2: the stride-2 input gradient dX (N, Hi, Wi, ci) fp32 NHWC (every pixel written) from the split
  *     output gradient (N, Ho, Wo, co) and wq = avse_sconv_wprep(co, ci, W, transposed = 2) (the 4 parity phases'
  *     taps, same byte count); replaces the stride-2 blocks' input gradient of resnet.py:26-67 (conv1 of layer2..4)

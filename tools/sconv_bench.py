@@ -1,6 +1,9 @@
 """Micro-benchmark of csrc/sconv.hip (split-fp16 MFMA 3x3 trunk convs) vs MIOpen fp32 at the avse1 C2 lip-trunk shapes
 (2400 frames, channels-last): forward, input gradient (stride 1 and the stride-2 phases), weight gradient; split passes timed apart.
-One JSON line per layer shape; frac_fp32 = fp32 algorithmic TFLOP/s / 157.3, frac_f16x3 = / (2500 / 3)."""
+One JSON line per layer shape; frac_fp32 = fp32 algorithmic TFLOP/s / 157.3, frac_f16x3 = / (2500 / 3).
+--avse4: the avse4 trunk shapes (2000 frames of 28 / 14 / 7 / 4 pixels).  --wgrad-only: only the weight gradient (its
+kernel, the partial-slab write and the reduce), --repeats times per shape, one JSON line per repeat; --tag names the
+library under test in each line (A/B runs load another build through AVSE_HIP_LIB)."""
 import argparse
 import json
 import os
@@ -33,14 +36,28 @@ def ev_ms(fn, n=5):
 
 def main():
     p = argparse.ArgumentParser()
-    p.add_argument("--frames", type=int, default=2400)
+    p.add_argument("--frames", type=int, default=None, help="default: 2400, with --avse4 2000")
     p.add_argument("--no-miopen", action="store_true")
+    p.add_argument("--avse4", action="store_true", help="the avse4 trunk shapes")
+    p.add_argument("--wgrad-only", action="store_true", help="time only the weight gradient (with its reduce)")
+    p.add_argument("--stride1-only", action="store_true")
+    p.add_argument("--ci", type=int, default=0, help="only the shapes with this many input channels")
+    p.add_argument("--repeats", type=int, default=1, help="--wgrad-only: timed repeats per shape")
+    p.add_argument("--tag", default="", help="copied into every JSON line")
     args = p.parse_args()
     dev = "cuda"
     torch.backends.cudnn.benchmark = False
-    shapes = [(64, 24, 64, 1), (64, 24, 128, 2), (128, 12, 128, 1), (128, 12, 256, 2), (256, 6, 256, 1),
-              (256, 6, 512, 2), (512, 3, 512, 1)]
-    N = args.frames
+    sizes = (28, 14, 7, 4) if args.avse4 else (24, 12, 6, 3)
+    shapes = []
+    for k, h in enumerate(sizes):
+        shapes.append((64 << k, h, 64 << k, 1))
+        if k < 3:
+            shapes.append((64 << k, h, 128 << k, 2))
+    if args.stride1_only:
+        shapes = [sh for sh in shapes if sh[3] == 1]
+    if args.ci:
+        shapes = [sh for sh in shapes if sh[0] == args.ci]
+    N = args.frames or (2000 if args.avse4 else 2400)
     for ci, H, co, s in shapes:
         g = torch.Generator(device=dev).manual_seed(ci + co)
         x = torch.randn((N, ci, H, H), device=dev, generator=g).contiguous(memory_format=CL)
@@ -59,6 +76,16 @@ def main():
             r[name] = {"ms": round(ms, 3), "tflops": round(tf, 1), "frac_fp32": round(tf / 157.3, 3),
                        "frac_f16x3": round(tf / (2500 / 3), 3)}
 
+        if args.wgrad_only:
+            for rep in range(args.repeats):
+                ms = ev_ms(lambda: K.sconv_wgrad((xq, xm), (dq, dm), tuple(x.shape), co, s), n=10)
+                tf = flops / (ms * 1e-3) / 1e12
+                print(json.dumps({"tag": args.tag, "shape": r["shape"], "gflop": r["gflop"], "rep": rep,
+                                  "wgrad_ms": round(ms, 4), "tflops": round(tf, 1),
+                                  "frac_f16x3": round(tf / (2500 / 3), 3)}), flush=True)
+            del x, dy, xq, dq
+            torch.cuda.empty_cache()
+            continue
         rec("split_fwd", ev_ms(lambda: K.sconv_fwd((xq, xm), tuple(x.shape), w, s)))
         r["split_x_ms"] = round(ev_ms(lambda: K.split_nhwc(x, xm)), 3)
         if s == 1:
