@@ -234,6 +234,7 @@ SIGNATURES = {
     "avse_dconv_wprep2": (c_i32, [c_vp] * 6),
     "avse_dconv_wgrad16_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64]),
     "avse_dconv_wgrad16": (c_i32, [c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "avse_dconv_wgrad16_plan": (c_i32, [c_i64, c_i64, c_i64, c_i64, c_vp]),
     "avse_conv1_fwd": (c_i32, [c_i64] * 3 + [c_vp] * 5),
     "avse_conv1_dgrad": (c_i32, [c_i64] * 3 + [c_vp] * 4),
     "avse_conv1_wgrad_workspace_bytes": (c_i64, [c_i64] * 3),

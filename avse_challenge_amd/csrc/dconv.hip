@@ -263,228 +263,25 @@ __global__ __launch_bounds__(64 * NW, WGS) void fwd_kernel(Args a) {
 // ------------------------------------------------------------------------------------------------ weight gradient
 // dW[o][i][kh][kw] = sum_{n,h,w} dY[n][h][w][o] X[n][h + d (kh - 2)][w + d (kw - 2)][i] from the two Q4-split operands
 // (X split in the forward, dY for the input gradient), scaled back by 2^-(e_dy + e_x).  Per-tap GEMM with M = o, N = i
-// and the reduction over pixels: workgroup (chunk range r, kernel row kh) runs over a contiguous range of 64-pixel raster
-// chunks; per chunk the dY rows and the input segment of row kh (positions as in the forward: the chunk's pixels of one
-// or two rows, 2d halo, 4d gap) are staged by LDS-DMA.  8 waves: wave (half, o block, i block) accumulates the 5 kw tiles
-// (80 accumulators per lane) over k-steps {2 half, 2 half + 1} of every chunk, so two waves share each SIMD (one
-// wave's fragment reads and DMA issue run under the other's MFMAs; round 5's 4-wave form left one wave per SIMD, whose
-// LDS latency and per-chunk address work were exposed: 0.25 of the split peak in the avse1 step).  Both operands are
-// contiguous along the GEMM's M / N (channels), so the fragments are read with ds_read_b64_tr_b16 (4 pixels x 16
-// channels per 16-lane group, delivered transposed) from 256-B pixel rows whose 16-B chunk c sits at c ^ ((r & 3) << 2).
-// The kh = 0 workgroups add one more MFMA pair per k-step against a ones fragment: the bias gradient db[o] = sum dY[.][o].
-// The chunk positions advance incrementally (no integer division in the loop).  Per-(workgroup, half) partial slabs,
-// summed in a fixed order by a second kernel (deterministic).
-constexpr int WG_CHUNK = 64;                     // pixels per chunk (4 k-steps of 16)
+// and the reduction over pixels.  Both operands are contiguous along the GEMM's M / N (channels), so the fragments are
+// read with ds_read_b64_tr_b16 (4 pixels x 16 channels per 16-lane group, delivered transposed) from swizzled pixel
+// rows.  One more MFMA pair per k-step against a ones fragment gives the bias gradient db[o] = sum dY[.][o].  Partial
+// slabs per workgroup pair, summed in a fixed order by a second kernel (deterministic).
+constexpr int WG_CHUNK = 64;                     // pixels per column chunk (4 k-steps of 16); the narrowest row
 constexpr int PIXB = 256;                        // LDS / Q4 bytes per pixel
-constexpr int WTHREADS = 512, WWAVES = WTHREADS / 64;
 
 typedef short s4_t __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) s4_t lds_s4_t;
 
-// 16-B chunk c of staged pixel row r sits at physical chunk tswz(r, c).  A transposed fragment read (tfrag) takes, per
+// 16-B chunk c of staged pixel row r sits at physical chunk tswz(r, c).  A transposed fragment read (LaneOff) takes, per
 // 32-lane half, 4 consecutive rows x 4 chunks whose logical indices differ in bits 0 and 2; the rows' XOR masks must
 // then differ in bits 1 and 3 for the 16 (row, chunk) pairs to land on 16 distinct 4-bank groups (every row starts on
 // bank 0: 256-B rows).  Round 5's mask ((r & 3) << 2) moved bits 2-3 only: 2-way conflicts on every read
 // (SQ_LDS_BANK_CONFLICT = 0.5 x SQ_LDS_IDX_ACTIVE, gpurun_out/r06f_pmc_dconv); this one is conflict-free.
 __device__ inline int tswz(int r, int c) { return c ^ (((r & 1) << 1) | ((r & 2) << 2)); }
 
-// MFMA operand fragment (32 channels x 16 pixels) of the channel block cb (quarters 2 cb, 2 cb + 1), plane pl (0 hi,
-// 1 lo), k-step rows rows[0..15] given per lane: lane l (group g = l >> 4, i = l & 15) reads pixel rows
-// row(8 (g >> 1) + (i >> 2) + 4 u), channels 16 (g & 1) + 4 (i & 3) .. + 3 of the block
-__device__ inline half8 tfrag(const uint8_t* img, const int (&row)[2], int cb, int pl, int lane) {
-    const int g = lane >> 4, i = lane & 15;
-    const int q = 2 * cb + (g & 1);
-    s4_t v[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        const int r = row[u];
-        const int byte = q * 64 + pl * 32 + 8 * (i & 3);                 // within the pixel's 256 B
-        const int off = r * PIXB + 16 * tswz(r, byte >> 4) + (byte & 15);
-        v[u] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(img + off));
-    }
-    const s4_t w0 = v[0], w1 = v[1];
-    const short __attribute__((ext_vector_type(8))) w = {w0[0], w0[1], w0[2], w0[3], w1[0], w1[1], w1[2], w1[3]};
-    return __builtin_bit_cast(half8, w);
-}
-
-struct WArgs {
-    const void* xq;
-    const void* dyq;
-    const uint32_t* xmax;
-    const uint32_t* dymax;
-    float* part;                 // [ranges][2][kh][kw][o][i]
-    float* dbpart;               // [ranges][2][o] (kh = 0 workgroups) or NULL
-    int N, H, W, cpi, chunks, ranges;
-};
-
-// a chunk's position: image n, first raster pixel p0 in it, its row hA and column wA0
-struct ChunkPos {
-    int n, p0, hA, wA0;
-    __device__ void init(int c, int cpi, int W) {
-        n = c / cpi;
-        p0 = (c - n * cpi) * WG_CHUNK;
-        hA = p0 / W;
-        wA0 = p0 - hA * W;
-    }
-    __device__ void next(int HW, int W) {                // W >= WG_CHUNK
-        p0 += WG_CHUNK;
-        if (p0 >= HW) {
-            ++n;
-            p0 = hA = wA0 = 0;
-        } else {
-            wA0 += WG_CHUNK;
-            if (wA0 >= W) {
-                wA0 -= W;
-                ++hA;
-            }
-        }
-    }
-};
-
-template <int D>
-__global__ __launch_bounds__(WTHREADS, 1) void wgrad_kernel(WArgs a) {
-    constexpr int NP = WG_CHUNK + 8 * D;           // staged input positions per chunk
-    constexpr int YIMG = WG_CHUNK * PIXB, XIMG = NP * PIXB, STG = YIMG + XIMG;
-    constexpr int NB = (3 * STG <= 160 * 1024) ? 3 : 2;
-    constexpr int PY = YIMG / 1024, PT = PY + XIMG / 1024;       // pieces per chunk (4 pixels per 1-KB piece)
-    constexpr int MAXPW = PT / WWAVES + 1;
-    __shared__ __attribute__((aligned(1024))) uint8_t lds[NB * STG];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int bid = xcd_remap(blockIdx.x, gridDim.x);       // the 5 kh workgroups of a range share an XCD's L2
-    const int r = bid / KS, kh = bid % KS;
-    const int c_lo = (int)((int64_t)r * a.chunks / a.ranges), c_hi = (int)((int64_t)(r + 1) * a.chunks / a.ranges);
-    const int HW = a.H * a.W;
-    const i4_t rx = dma_rsrc(a.xq, (int64_t)a.N * HW * PIXB);
-    const i4_t ry = dma_rsrc(a.dyq, (int64_t)a.N * HW * PIXB);
-    const uint32_t lds0 = lds_u32(lds);
-    const int npieces = (PT - wave + WWAVES - 1) / WWAVES;
-    const int pr = lane >> 4, pc = lane & 15;                    // a piece's lane: row (of 4), physical chunk
-    // per piece of this wave: the lane's pixel (dY) or position (X) within the chunk and its swizzled chunk byte offset
-    int pj[MAXPW];
-    uint32_t psw[MAXPW];
-#pragma unroll
-    for (int m = 0; m < MAXPW; ++m) {
-        const int k = wave + WWAVES * m;
-        pj[m] = k < PY ? 4 * k + pr : 4 * (k - PY) + pr;
-        psw[m] = 16u * tswz(pj[m], pc);
-    }
-
-    auto issue = [&](const ChunkPos& cp, int buf) {
-        const int nA = min(WG_CHUNK, a.W - cp.wA0);
-        const int row1 = cp.hA + D * (kh - 2), row2 = nA < WG_CHUNK ? row1 + 1 : -1000000;
-        const int ybase = cp.n * HW + cp.p0;                     // dY pixel of chunk position 0
-        const int nHrow = cp.n * a.H;
-        const uint32_t img = lds0 + buf * STG;
-#pragma unroll
-        for (int m = 0; m < MAXPW; ++m) {
-            if (m >= npieces) break;
-            const int k = wave + WWAVES * m;
-            if (k < PY) {                                        // dY rows: chunk pixel j
-                const int j = pj[m];
-                const uint32_t off = cp.p0 + j < HW ? (uint32_t)(ybase + j) * PIXB + psw[m] : 0x7FFFFFF0u;
-                dma16(ry, img + k * 1024, off);
-            } else {
-                const int q = pj[m];                             // input position
-                const bool s1 = q < nA + 4 * D;
-                const int col = s1 ? cp.wA0 - 2 * D + q : q - nA - 6 * D;
-                const int row = s1 ? row1 : row2;
-                const bool ok = (unsigned)col < (unsigned)a.W && (unsigned)row < (unsigned)a.H;
-                const uint32_t pix = (uint32_t)((nHrow + row) * a.W + col);
-                dma16(rx, img + YIMG + (k - PY) * 1024, ok ? pix * PIXB + psw[m] : 0x7FFFFFF0u);
-            }
-        }
-    };
-
-    const int half = wave >> 2, ob = (wave >> 1) & 1, ib = wave & 1;   // k-steps {2 half, 2 half + 1}, (o, i) block
-    const bool want_db = a.dbpart != nullptr && kh == 0 && ib == 0;      // wave-uniform
-    floatx16 acc[KS], accb;
-#pragma unroll
-    for (int k = 0; k < KS; ++k)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[k][e] = 0.f;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) accb[e] = 0.f;
-    half8 ones;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) ones[e] = (_Float16)1.0f;
-
-    const int g = lane >> 4, li = lane & 15;
-    ChunkPos cc, ci;                                             // compute cursor (chunk c), issue cursor
-    cc.init(c_lo, a.cpi, a.W);
-    ci = cc;
-    if (c_lo < c_hi) {
-        issue(ci, 0);
-        ci.next(HW, a.W);
-    }
-    if (NB == 3 && c_lo + 1 < c_hi) {
-        issue(ci, 1);
-        ci.next(HW, a.W);
-    }
-    for (int c = c_lo; c < c_hi; ++c) {
-        const int it = c - c_lo;
-        const bool ahead = NB == 3 && c + 1 < c_hi;              // the next chunk's pieces may still fly
-        if (ahead) wait_all_but(npieces);
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if (c + NB - 1 < c_hi) {
-            issue(ci, (it + NB - 1) % NB);
-            ci.next(HW, a.W);
-        }
-        const uint8_t* yimg = lds + (it % NB) * STG;
-        const uint8_t* ximg = yimg + YIMG;
-        const int nA = min(WG_CHUNK, a.W - cc.wA0);
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-            const int s = 2 * half + s2;
-            int ry_[2], rx_[2];
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const int j = 16 * s + 8 * (g >> 1) + (li >> 2) + 4 * u;       // the lane's pixel of the k-step
-                ry_[u] = j;
-                rx_[u] = j < nA ? j : j + 4 * D;
-            }
-            const half8 ah = tfrag(yimg, ry_, ob, 0, lane), al = tfrag(yimg, ry_, ob, 1, lane);
-#pragma unroll
-            for (int kw = 0; kw < KS; ++kw) {
-                const int rk[2] = {rx_[0] + D * kw, rx_[1] + D * kw};
-                const half8 bh = tfrag(ximg, rk, ib, 0, lane), bl = tfrag(ximg, rk, ib, 1, lane);
-                acc[kw] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[kw], 0, 0, 0);
-                acc[kw] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc[kw], 0, 0, 0);
-                acc[kw] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc[kw], 0, 0, 0);
-            }
-            if (want_db) {
-                accb = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, ones, accb, 0, 0, 0);
-                accb = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, ones, accb, 0, 0, 0);
-            }
-        }
-        cc.next(HW, a.W);
-    }
-    // partial tiles: acc[kw] register 4 q + e = row o = 32 ob + 8 q + 4 (lane >> 5) + e, column i = 32 ib + (lane & 31)
-    const float sc = __builtin_ldexpf(1.f, -(split_exp(*a.xmax) + split_exp(*a.dymax)));
-    float* pp = a.part + (((int64_t)r * 2 + half) * KS + kh) * KS * C * C;
-#pragma unroll
-    for (int kw = 0; kw < KS; ++kw)
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int o = 32 * ob + 8 * q + 4 * (lane >> 5) + e, i = 32 * ib + (lane & 31);
-                pp[((int64_t)kw * C + o) * C + i] = acc[kw][4 * q + e] * sc;
-            }
-    if (want_db && (lane & 31) == 0) {
-        const float sd = __builtin_ldexpf(1.f, -split_exp(*a.dymax));
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                a.dbpart[((int64_t)r * 2 + half) * C + 32 * ob + 8 * q + 4 * (lane >> 5) + e] = accb[4 * q + e] * sd;
-    }
-}
-
-// dW[o][i][kh][kw] = sum over slabs of part[slab][kh][kw][o][i]; db[o] = sum over slabs of dbpart[slab][o] (slab =
-// 2 range + half, summed in order: deterministic)
+// dW[o][i][kh][kw] = sum over slabs of part[slab][kh][kw][o][i]; db[o] = sum over slabs of dbpart[slab][o] (summed
+// in order: deterministic)
 __global__ void wgrad_reduce_kernel(const float* __restrict__ part, const float* __restrict__ dbpart, int slabs,
                                     float* __restrict__ dw, float* __restrict__ db) {
     constexpr int TOTAL = KS * KS * C * C;
@@ -503,7 +300,331 @@ __global__ void wgrad_reduce_kernel(const float* __restrict__ part, const float*
     dw[((o * C + i) * KS + kh) * KS + kw] = v;
 }
 
-inline int wgrad_ranges(int chunks) { return std::max(1, std::min(chunks, 256 / KS * 1)); }
+
+// ------------------------------------------------------------------- weight gradient, rows walked in steps of d
+// The same sums from a walk in which every input segment and every dY segment is staged once for all 25 taps.  Output
+// rows rho, rho + d, rho + 2 d, ... of one residue class rho = h mod d need input rows of that class only, and each
+// needs exactly one row its predecessor did not: row h + 2 d.
+//   unit  = (image n, residue class rho, column chunk, input-channel half ib); a column chunk is 64 columns, the last
+//           one the rest of the row, or 64 + the rest where the rest is <= 16 columns (W = 257: 64, 64, 64, 65), so a
+//           chunk has 1 .. 5 k-steps of 16 pixels;
+//   step  = output row h = rho + t d of the unit: the chunk's dY pixels (256 B each, one of 2 buffers) against the five
+//           input segments of rows h - 2 d .. h + 2 d, columns w0 - 2 d .. w0 + 16 ks + 2 d, the ib half only (128 B
+//           per position), which sit in a ring of 6 slots: row index tau = t + kh - 2 of the class in slot (tau + 2)
+//           mod 6.  Output pixel j reads position j + d kw of the slot of its kernel row.  While step t computes, the
+//           one new segment of step t + 1 (row index t + 3, into the slot step t - 1 read last) and the next dY
+//           segment are staged; their LDS-DMA pieces are issued between the MFMAs of the wave's first k-step.
+// Rows and columns outside the image, and dY pixels beyond the chunk's width (the dead pixels of a partial k-step),
+// are staged through the out-of-range offset and land as zeros: every byte a fragment reads was written by the DMA of
+// the step or unit that reads it, nothing is assumed of the LDS contents, and a unit restarts the ring (5 segments).
+// Workgroups are persistent: workgroup b (after xcd_remap) takes units b, b + G, b + 2 G, ... of the list ordered
+// (n, rho, chunk, ib), ib fastest, so that at any time 8 neighbouring workgroups of one XCD share one (n, rho)'s rows
+// and dY in its L2.  G is even, so a workgroup keeps its ib.  4 waves, one per SIMD: wave = (o block of 32, tap set)
+// owns 32 o x 32 i x 13 taps (0 .. 12: set 0) or 12 taps (13 .. 24: set 1, which also carries the bias gradient's ones
+// fragment in the ib = 0 workgroups) over every k-step of the chunk: 156 / 152 MFMAs per wave behind each barrier at 64
+// columns.  (One wave with all 25 taps over half the k-steps, 400 accumulators, does not build: with one wave per
+// SIMD hipcc places MFMA accumulators in the 256 AGPRs only and copies the rest in and out around every MFMA; 13
+// tiles + the bias tile are 224.)  The workgroup writes the ib columns of slab b / 2; wgrad_reduce_kernel sums the
+// G / 2 slabs in order: no atomics.
+namespace rows {
+
+constexpr int RTHREADS = 256;
+constexpr int XPIXB = 128;                       // ring bytes per input position (one input-channel half)
+constexpr int CWMAX = 80;                        // widest column chunk: 5 k-steps
+constexpr int NSLOT = 6;
+constexpr int YBUF = CWMAX * PIXB;               // one dY buffer (20 KB)
+constexpr int TAPS0 = 13;                        // taps of set 0; set 1 takes the other 12
+constexpr int MAXWG = 256;                       // one workgroup per CU
+
+constexpr int slot_bytes(int D) { return (CWMAX + 4 * D) * XPIXB; }
+constexpr int lds_bytes(int D) { return NSLOT * slot_bytes(D) + 2 * YBUF; }
+static_assert(lds_bytes(MAXD) <= 160 * 1024, "LDS");
+static_assert(slot_bytes(2) % 1024 == 0, "whole DMA pieces");
+
+// column chunks of a row of W >= 64 columns; chunk c starts at 64 c, the last one ends the row
+inline __host__ __device__ int chunks_of(int W) { return W / 64 + (W % 64 > 16 ? 1 : 0); }
+
+struct Plan {
+    int nck, nwg, slabs, lds;
+    int64_t units, steps, pieces;
+};
+
+// The static plan of a launch.  pieces = 1-KB LDS-DMA wave-instructions: a unit of T > 0 steps stages 5 input
+// segments and T - 1 more (npx = (16 ks + 4 D) / 8 pieces each) and T dY segments (4 ks pieces); empty units stage
+// nothing.
+inline Plan make_plan(int64_t N, int64_t H, int64_t W, int D) {
+    Plan p;
+    p.nck = chunks_of((int)W);
+    p.units = N * p.nck * D * 2;
+    p.nwg = (int)std::min<int64_t>(MAXWG, p.units);
+    p.slabs = p.nwg / 2;
+    p.lds = lds_bytes(D);
+    p.steps = 0;
+    p.pieces = 0;
+    for (int c = 0; c < p.nck; ++c) {
+        const int cw = c == p.nck - 1 ? (int)W - 64 * c : 64, ks = (cw + 15) / 16, npx = (16 * ks + 4 * D) / 8;
+        for (int rho = 0; rho < D; ++rho) {
+            const int64_t T = rho < H ? (H - rho + D - 1) / D : 0;
+            if (T == 0) continue;
+            p.steps += 2 * N * T;
+            p.pieces += 2 * N * ((T + 4) * npx + T * 4 * ks);
+        }
+    }
+    return p;
+}
+
+struct RArgs {
+    const void* xq;
+    const void* dyq;
+    const uint32_t* xmax;
+    const uint32_t* dymax;
+    float* part;                 // [slabs][kh][kw][o][i]
+    float* dbpart;               // [slabs][o] or NULL
+    int N, H, W, nck, units;
+};
+
+// The lane's addresses of the MFMA operand fragments (32 channels x 16 pixels), as LDS byte offsets: a k-step adds one
+// wave-uniform base per kernel row and the tap's columns ride in the instruction's offset field.  Lane l (g = l >> 4,
+// i = l & 15)
+// reads pixel p_u = 8 (g >> 1) + (i >> 2) + 4 u of the k-step, u = 0, 1, channels 16 (g & 1) + 4 (i & 3) .. + 3 of its
+// 32-channel block, plane pl (0 hi, 1 lo):
+//   y[u][pl]: dY buffer, 256-B pixels, tswz (the block is ob); + 4096 s for k-step s (16 pixels: p & 3 unchanged);
+//   x[u][pl]: ring slot, 128-B positions (quarters 0, 1 of the unit's ib half) whose 16-B chunk c sits at c ^ (r & 2);
+//             + 128 (16 s + d kw) for k-step s and tap column kw.  d kw is even: where it has bit 1 set (d = 2, kw odd)
+//             the position's mask flips, which is the other plane's address: chunk c = 4 (g & 1) + 2 pl + (i & 3) / 2.
+// A 32-lane half reads 4 consecutive positions x 4 chunks that differ in bits 0 and 2; even and odd positions lie in
+// opposite halves of the 256-B bank row and the mask separates the two of each parity: conflict-free, as tswz is.
+struct LaneOff {
+    uint32_t x[2][2], y[2][2];
+    __device__ void init(int lane, int ob) {
+        const int g = lane >> 4, i = lane & 15;
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+            for (int pl = 0; pl < 2; ++pl) {
+                const int p = 8 * (g >> 1) + (i >> 2) + 4 * u;
+                const int bx = (g & 1) * 64 + pl * 32 + 8 * (i & 3);
+                x[u][pl] = (uint32_t)(p * XPIXB + 16 * ((bx >> 4) ^ (p & 2)) + (bx & 15));
+                const int by = (2 * ob + (g & 1)) * 64 + pl * 32 + 8 * (i & 3);
+                y[u][pl] = (uint32_t)(p * PIXB + 16 * tswz(p, by >> 4) + (by & 15));
+            }
+    }
+};
+
+template <int OFF>
+__device__ __forceinline__ half8 frag2(uint32_t a0, uint32_t a1) {
+    const s4_t w0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(uintptr_t)(a0 + OFF));
+    const s4_t w1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_t*)(uintptr_t)(a1 + OFF));
+    const short __attribute__((ext_vector_type(8))) w = {w0[0], w0[1], w0[2], w0[3], w1[0], w1[1], w1[2], w1[3]};
+    return __builtin_bit_cast(half8, w);
+}
+
+// the fragments a k-step starts from: its dY (A) pair and the input (B) pair of its first tap
+struct Frags {
+    half8 ah, al, bh, bl;
+};
+
+__device__ __forceinline__ void load_a(const LaneOff& lo, uint32_t ybase, half8& ah, half8& al) {
+    ah = frag2<0>(ybase + lo.y[0][0], ybase + lo.y[1][0]);
+    al = frag2<0>(ybase + lo.y[0][1], ybase + lo.y[1][1]);
+}
+
+// tap TAP's input pair: xb = the k-step's first position in the slot of the tap's kernel row.  The tap's column offset
+// is a constant of the instruction; (d kw) & 2 swaps the planes' addresses (LaneOff)
+template <int D, int TAP>
+__device__ __forceinline__ void load_b(const LaneOff& lo, const uint32_t (&xbase)[KS], half8& bh, half8& bl) {
+    constexpr int KH = TAP / KS, KW = TAP % KS, F_ = ((D * KW) >> 1) & 1, O_ = D * KW * XPIXB;
+    const uint32_t xb = xbase[KH];
+    bh = frag2<O_>(xb + lo.x[0][F_], xb + lo.x[1][F_]);
+    bl = frag2<O_>(xb + lo.x[0][1 - F_], xb + lo.x[1][1 - F_]);
+}
+
+// One k-step, taps T0 .. T1 - 1 (accumulators acc[tap - T0]): ybase / xbase[kh] = LDS addresses of the k-step's first
+// dY pixel and of its first position in kernel row kh's slot.  One wave per SIMD has nobody to hide its LDS latency, so
+// the fragments run one tap ahead: f holds the k-step's first fragments on entry; every tap reads the next tap's input
+// pair before its own three MFMAs, and the last tap reads the next k-step's first fragments into f (has_next).
+// piece(k), k = 0 .. 9, issues the wave's k-th staging piece of the next step behind tap T0 + k (ISSUE only).
+template <int D, int T0, int T1, bool ISSUE, typename F>
+__device__ __forceinline__ void kstep(floatx16 (&acc)[TAPS0], floatx16& accb, const LaneOff& lo, uint32_t ybase,
+                                      const uint32_t (&xbase)[KS], bool want_db, F&& piece, Frags& f, bool has_next) {
+    const half8 ah = f.ah, al = f.al;
+    half8 bh = f.bh, bl = f.bl;
+#pragma unroll
+    for (int tap = T0; tap < T1; ++tap) {
+        half8 nh = bh, nl = bl;
+        if (tap + 1 < T1) {
+            // (the unrolled loop's tap is a constant; the switch names it for the template argument)
+#define AVSE_ROWS_NEXT(K) case T0 + K: load_b<D, (T0 + K + 1 < KS * KS ? T0 + K + 1 : 0)>(lo, xbase, nh, nl); break;
+            switch (tap) {
+                AVSE_ROWS_NEXT(0) AVSE_ROWS_NEXT(1) AVSE_ROWS_NEXT(2) AVSE_ROWS_NEXT(3) AVSE_ROWS_NEXT(4)
+                AVSE_ROWS_NEXT(5) AVSE_ROWS_NEXT(6) AVSE_ROWS_NEXT(7) AVSE_ROWS_NEXT(8) AVSE_ROWS_NEXT(9)
+                AVSE_ROWS_NEXT(10) AVSE_ROWS_NEXT(11)
+                default: break;
+            }
+#undef AVSE_ROWS_NEXT
+        } else if (has_next) {
+            uint32_t xn[KS];
+#pragma unroll
+            for (int kh = 0; kh < KS; ++kh) xn[kh] = xbase[kh] + 16 * XPIXB;
+            load_a(lo, ybase + 16 * PIXB, f.ah, f.al);
+            load_b<D, T0>(lo, xn, f.bh, f.bl);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        acc[tap - T0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[tap - T0], 0, 0, 0);
+        acc[tap - T0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc[tap - T0], 0, 0, 0);
+        acc[tap - T0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc[tap - T0], 0, 0, 0);
+        if constexpr (ISSUE) {
+            if (tap - T0 < 10) piece(tap - T0);
+        }
+        bh = nh;
+        bl = nl;
+    }
+    if (want_db) {
+        half8 ones;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) ones[e] = (_Float16)1.0f;
+        accb = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, ones, accb, 0, 0, 0);
+        accb = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, ones, accb, 0, 0, 0);
+    }
+}
+
+// a wave's whole launch, TS = its tap set (a template parameter: the two sets' code shares no accumulator registers)
+template <int D, int TS>
+__device__ __forceinline__ void wave_body(const RArgs& a, uint8_t* lds, int wave, int lane) {
+    constexpr int SLOTB = slot_bytes(D), RING = NSLOT * SLOTB;
+    constexpr int T0 = TS == 0 ? 0 : TAPS0, T1 = TS == 0 ? TAPS0 : KS * KS, ts = TS;
+    const int nwg = gridDim.x;                                    // even
+    const int bid = xcd_remap(blockIdx.x, nwg);
+    const int ib = bid & 1, ob = wave & 1;                       // input-channel half, o block
+    const int HW = a.H * a.W;
+    const i4_t rx = dma_rsrc(a.xq, (int64_t)a.N * HW * PIXB);
+    const i4_t ry = dma_rsrc(a.dyq, (int64_t)a.N * HW * PIXB);
+    const uint32_t lds0 = lds_u32(lds);
+    // the lane's share of a staging piece.  dY piece 4 m + wave: pixel 16 m + ypx0 (4 pixels x 16 chunks per piece);
+    // input piece 4 m + wave: position 32 m + xpos0 (8 positions x 8 chunks); the swizzles do not depend on m
+    const int ypx0 = 4 * wave + (lane >> 4), xpos0 = 8 * wave + (lane >> 3);
+    const uint32_t ysw = 16u * tswz(lane >> 4, lane & 15);
+    const uint32_t xsw = (uint32_t)(ib * XPIXB) + 16u * ((lane & 7) ^ ((lane >> 3) & 2));
+    const bool want_db = TS == 1 && a.dbpart != nullptr && ib == 0;
+    LaneOff lo;
+    lo.init(lane, ob);
+
+    floatx16 acc[TAPS0], accb;
+#pragma unroll
+    for (int k = 0; k < TAPS0; ++k)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[k][e] = 0.f;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) accb[e] = 0.f;
+
+    for (int u = bid; u < a.units; u += nwg) {
+        int rest = u >> 1;
+        const int cc = rest % a.nck;
+        rest /= a.nck;
+        const int rho = rest % D, n = rest / D;
+        const int T = rho < a.H ? (a.H - rho + D - 1) / D : 0;
+        if (T == 0) continue;
+        const int w0 = 64 * cc, cw = cc == a.nck - 1 ? a.W - w0 : 64;
+        const int ks = (cw + 15) >> 4, npx = (16 * ks + 4 * D) >> 3;
+        const int nH = n * a.H;
+        // dY piece m of row index t into buffer t & 1; input piece m of row index tau into its slot
+        auto dma_y = [&](int m, int t) {
+            const int px = ypx0 + 16 * m;
+            const int pix = (nH + rho + t * D) * a.W + w0 + px;
+            dma16(ry, lds0 + RING + (t & 1) * YBUF + (wave + 4 * m) * 1024,
+                  px < cw ? (uint32_t)pix * PIXB + ysw : 0x7FFFFFF0u);
+        };
+        auto dma_x = [&](int m, int tau, int slot) {
+            const int row = rho + tau * D, col = w0 - 2 * D + xpos0 + 32 * m;
+            const bool ok = tau >= 0 && row < a.H && (unsigned)col < (unsigned)a.W;
+            const int pix = (nH + row) * a.W + col;
+            dma16(rx, lds0 + slot * SLOTB + (wave + 4 * m) * 1024, ok ? (uint32_t)pix * PIXB + xsw : 0x7FFFFFF0u);
+        };
+        // restart the ring: every wave is past the previous unit's last fragment read, nothing is in flight
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+#pragma unroll 1
+        for (int tau = -2; tau <= 2; ++tau)
+            for (int m = 0; wave + 4 * m < npx; ++m) dma_x(m, tau, tau + 2);
+        for (int m = 0; m < ks; ++m) dma_y(m, 0);
+        int s0 = 0;                                              // slot of row index t - 2
+#pragma unroll 1
+        for (int t = 0; t < T; ++t) {
+            // everything staged for this step has landed (this wave's pieces; the barrier: every wave's), and every
+            // wave is past step t - 1, whose slot and dY buffer the pieces issued below overwrite
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+            int sb[KS];
+#pragma unroll
+            for (int kh = 0; kh < KS; ++kh) sb[kh] = (s0 + kh >= NSLOT ? s0 + kh - NSLOT : s0 + kh) * SLOTB;
+            const int snew = s0 + 5 >= NSLOT ? s0 + 5 - NSLOT : s0 + 5;
+            const bool more = t + 1 < T;
+            auto piece = [&](int k) {
+                if (!more) return;
+                const int m = k >> 1;
+                if (k & 1) {
+                    if (wave + 4 * m < npx) dma_x(m, t + 3, snew);
+                } else {
+                    if (m < ks) dma_y(m, t + 1);
+                }
+            };
+            const uint32_t ybuf = lds0 + RING + (t & 1) * YBUF;
+            // k-step s: dY pixels 16 s .. 16 s + 15 and, in every slot, the positions from 16 s on; the next step's
+            // pieces go out behind the taps of k-step 0
+            uint32_t xb[KS];
+#pragma unroll
+            for (int kh = 0; kh < KS; ++kh) xb[kh] = lds0 + sb[kh];
+            Frags f;
+            load_a(lo, ybuf, f.ah, f.al);
+            load_b<D, T0>(lo, xb, f.bh, f.bl);
+            kstep<D, T0, T1, true>(acc, accb, lo, ybuf, xb, want_db, piece, f, ks > 1);
+#pragma unroll 1
+            for (int s = 1; s < ks; ++s) {
+#pragma unroll
+                for (int kh = 0; kh < KS; ++kh) xb[kh] += 16 * XPIXB;
+                kstep<D, T0, T1, false>(acc, accb, lo, ybuf + s * 16 * PIXB, xb, want_db, piece, f, s + 1 < ks);
+            }
+            s0 = s0 + 1 >= NSLOT ? 0 : s0 + 1;
+        }
+    }
+
+    // acc[k] = tap 13 ts + k; register 4 q + e = row o = 32 ob + 8 q + 4 (lane >> 5) + e, column i = 32 ib +
+    // (lane & 31)
+    const float sc = __builtin_ldexpf(1.f, -(split_exp(*a.xmax) + split_exp(*a.dymax)));
+    float* pp = a.part + ((int64_t)(bid >> 1) * KS * KS + TAPS0 * ts) * C * C;
+#pragma unroll
+    for (int k = 0; k < TAPS0; ++k) {
+        if (k < T1 - T0) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int o = 32 * ob + 8 * q + 4 * (lane >> 5) + e, i = 32 * ib + (lane & 31);
+                    pp[((int64_t)k * C + o) * C + i] = acc[k][4 * q + e] * sc;
+                }
+        }
+    }
+    if (want_db && (lane & 31) == 0) {
+        const float sd = __builtin_ldexpf(1.f, -split_exp(*a.dymax));
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                a.dbpart[(int64_t)(bid >> 1) * C + 32 * ob + 8 * q + 4 * (lane >> 5) + e] = accb[4 * q + e] * sd;
+    }
+}
+
+template <int D>
+__global__ __launch_bounds__(RTHREADS, 1) void wgrad_rows_kernel(RArgs a) {
+    __shared__ __attribute__((aligned(1024))) uint8_t lds[lds_bytes(D)];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (wave < 2) wave_body<D, 0>(a, lds, wave, lane);
+    else wave_body<D, 1>(a, lds, wave, lane);
+}
+
+}  // namespace rows
 
 // ------------------------------------------------------------------------------------------------ operand preparation
 // max |x| over n floats -> atomicMax on the float bits (split16.h), one per 1024-thread workgroup of a 256-workgroup
@@ -648,18 +769,37 @@ int avse_dconv_wprep2(const float* w, void* wq, void* wq_t, uint32_t* maxbits, u
     return AVSE_OK;
 }
 
+static bool wgrad16_shape_ok(int64_t N, int64_t H, int64_t W, int64_t dil) {
+    if (N <= 0 || H <= 0 || W < WG_CHUNK || (dil != 2 && dil != 4 && dil != 8 && dil != 16)) return false;
+    return N * H * W * 256 < (1LL << 31) - 1024;                // 32-bit byte offsets into the split operands
+}
+
+// the slab count does not fall with the dilation (more units), so dilation 16's covers every launch of the shape
 int64_t avse_dconv_wgrad16_workspace_bytes(int64_t N, int64_t H, int64_t W) {
-    const int64_t chunks = N * ((H * W + WG_CHUNK - 1) / WG_CHUNK);
-    return 4 * 2 * (int64_t)wgrad_ranges((int)std::min<int64_t>(chunks, 1 << 30)) * (KS * KS * C * C + C);
+    if (!wgrad16_shape_ok(N, H, W, MAXD)) return 0;
+    return 4 * (int64_t)rows::make_plan(N, H, W, MAXD).slabs * (KS * KS * C * C + C);
+}
+
+int avse_dconv_wgrad16_plan(int64_t N, int64_t H, int64_t W, int64_t dil, int64_t out[6]) {
+    if (!out) return AVSE_EINVAL;
+    if (!wgrad16_shape_ok(N, H, W, dil)) return AVSE_ESHAPE;
+    const rows::Plan p = rows::make_plan(N, H, W, (int)dil);
+    out[0] = p.units;
+    out[1] = p.steps;
+    out[2] = p.pieces;
+    out[3] = p.slabs;
+    out[4] = p.lds;
+    out[5] = p.nwg;
+    return AVSE_OK;
 }
 
 int avse_dconv_wgrad16(int64_t N, int64_t H, int64_t W, int64_t dil, const void* xq, const uint32_t* xmax,
                        const void* dyq, const uint32_t* dymax, float* dw, float* db, float* workspace,
                        avse_stream_t stream) {
     if (!xq || !xmax || !dyq || !dymax || !dw || !workspace) return AVSE_EINVAL;
-    if (N <= 0 || H <= 0 || W < WG_CHUNK || (dil != 2 && dil != 4 && dil != 8 && dil != 16)) return AVSE_ESHAPE;
-    if (N * H * W * 256 >= (1LL << 31) - 1024) return AVSE_ESHAPE;
-    WArgs a;
+    if (!wgrad16_shape_ok(N, H, W, dil)) return AVSE_ESHAPE;
+    const rows::Plan p = rows::make_plan(N, H, W, (int)dil);
+    rows::RArgs a;
     a.xq = xq;
     a.dyq = dyq;
     a.xmax = xmax;
@@ -667,23 +807,22 @@ int avse_dconv_wgrad16(int64_t N, int64_t H, int64_t W, int64_t dil, const void*
     a.N = (int)N;
     a.H = (int)H;
     a.W = (int)W;
-    a.cpi = (int)((H * W + WG_CHUNK - 1) / WG_CHUNK);
-    a.chunks = (int)(N * a.cpi);
-    a.ranges = wgrad_ranges(a.chunks);
+    a.nck = p.nck;
+    a.units = (int)p.units;
     a.part = workspace;
-    a.dbpart = db ? workspace + (int64_t)2 * a.ranges * KS * KS * C * C : nullptr;
-    const dim3 grid((unsigned)(a.ranges * KS)), block(WTHREADS);
+    a.dbpart = db ? workspace + (int64_t)p.slabs * KS * KS * C * C : nullptr;
+    const dim3 grid((unsigned)p.nwg), block(rows::RTHREADS);
     hipStream_t st = (hipStream_t)stream;
     switch (dil) {
-        case 2: hipLaunchKernelGGL(wgrad_kernel<2>, grid, block, 0, st, a); break;
-        case 4: hipLaunchKernelGGL(wgrad_kernel<4>, grid, block, 0, st, a); break;
-        case 8: hipLaunchKernelGGL(wgrad_kernel<8>, grid, block, 0, st, a); break;
-        default: hipLaunchKernelGGL(wgrad_kernel<16>, grid, block, 0, st, a); break;
+        case 2: hipLaunchKernelGGL(rows::wgrad_rows_kernel<2>, grid, block, 0, st, a); break;
+        case 4: hipLaunchKernelGGL(rows::wgrad_rows_kernel<4>, grid, block, 0, st, a); break;
+        case 8: hipLaunchKernelGGL(rows::wgrad_rows_kernel<8>, grid, block, 0, st, a); break;
+        default: hipLaunchKernelGGL(rows::wgrad_rows_kernel<16>, grid, block, 0, st, a); break;
     }
     AVSE_CHECK_LAUNCH();
     constexpr int TOTAL = KS * KS * C * C;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((TOTAL + C + 255) / 256), dim3(256), 0, st, a.part, a.dbpart,
-                       2 * a.ranges, dw, db);
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((TOTAL + C + 255) / 256), dim3(256), 0, st, a.part, a.dbpart, p.slabs,
+                       dw, db);
     AVSE_CHECK_LAUNCH();
     return AVSE_OK;
 }

@@ -426,7 +426,8 @@ constexpr int NPW_MAX = 184;                    // staged input positions per ch
 
 __device__ inline int tswz(int r, int c) { return c ^ ((r & 3) << 2); }
 
-// 32 channels (block cb of a staged row) x 16 pixels, plane pl (0 hi, 1 lo), rows given per lane (dconv.hip tfrag);
+// 32 channels (block cb of a staged row) x 16 pixels, plane pl (0 hi, 1 lo), rows given per lane (the lanes and bytes
+// of dconv.hip LaneOff);
 // RB = bytes per staged row
 template <int RB>
 __device__ inline half8 tfrag(const uint8_t* img, const int (&row)[2], int cb, int pl, int lane) {

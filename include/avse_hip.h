@@ -686,11 +686,17 @@ int avse_sconv_dgrad1_bn(int64_t N, int64_t H, int64_t W, int64_t ci, int64_t co
                          const float* bn_stats, const float* gamma, const float* beta, int32_t act, const float* alpha,
                          int32_t alpha_n, int32_t want_max, float* rows, avse_stream_t stream);
 /* Weight (and bias) gradient of the same convolution from the split input xq (max bits *xmax) and the split output
- * gradient dyq (*dymax): dw (64, 64, 5, 5), db (64) or NULL; workspace avse_dconv_wgrad16_workspace_bytes(). */
+ * gradient dyq (*dymax): dw (64, 64, 5, 5), db (64) or NULL; workspace avse_dconv_wgrad16_workspace_bytes() (partial
+ * slabs, every one written by every launch).  N, H >= 1, W >= 64, dil in {2, 4, 8, 16}.  Persistent workgroups walk the
+ * rows of one residue class h mod dil in steps of dil, so that each input-row segment and each dy segment is staged
+ * once for all 25 taps; slabs are summed in a fixed order: no atomics, two calls give the same bits. */
 int64_t avse_dconv_wgrad16_workspace_bytes(int64_t N, int64_t H, int64_t W);
 int avse_dconv_wgrad16(int64_t N, int64_t H, int64_t W, int64_t dil, const void* xq, const uint32_t* xmax,
                        const void* dyq, const uint32_t* dymax, float* dw, float* db, float* workspace,
                        avse_stream_t stream);
+/* The static plan avse_dconv_wgrad16 launches with (host only, no GPU work): out = { units, steps, 1-KB LDS-DMA pieces
+ * per launch, partial slabs, LDS bytes per workgroup, workgroups }. */
+int avse_dconv_wgrad16_plan(int64_t N, int64_t H, int64_t W, int64_t dil, int64_t out[6]);
 
 /* ---------------------------------------------------------------- MBSTOI scoring (fp64) ------
  * The binaural intelligibility metric the AVSE-4 challenge ranks by (evaluation/avse4/objective_evaluation.py:60-69,
