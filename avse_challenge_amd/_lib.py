@@ -140,6 +140,11 @@ SIGNATURES = {
                                      c_i32, c_vp, c_vp, c_i64, c_i64, c_vp]),
     "avse_cconv_fwd_state_bf16": (c_i32, [c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64,
                                           c_i64, c_i32, c_vp, c_vp, c_i64, c_i64, c_vp]),
+    "avse_scan_fwd_len": (c_i32, [ctypes.POINTER(ScanFwdArgs), c_vp, c_vp]),
+    "avse_cconv_fwd_len": (c_i32, [c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64,
+                                   c_i32, c_i32, c_vp]),
+    "avse_cconv_fwd_len_bf16": (c_i32, [c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64,
+                                        c_i64, c_i32, c_i32, c_vp]),
     "avse_cconv_update": (c_i32, [c_i64, c_i64, c_i64, c_i32, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64,
                                   c_i32, c_vp]),
     "avse_add_rmsnorm_fwd": (c_i32, [c_i64, c_i64, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp]),

@@ -470,6 +470,93 @@ __global__ __launch_bounds__(THREADS) void bwd_short_kernel(int rows, int D, int
     }
 }
 
+// ---------------------------------------------------------------- ragged batches (inference)
+// avse_cconv_fwd_len: row (b, d) is convolved over its own n = clamp(lengths[b], 0, L) columns as the dense launch
+// convolves a row of n columns in the same layout, and out's columns n .. L - 1 are stored as +0.  The dense kernels
+// agree on the order (acc = bias, then the taps with k ascending) but not on the rounding: fwd_vec_kernel (vectorised
+// rows longer than SHORT_L) accumulates with fma, fwd_short_kernel and fwd_kernel round each product and then add.  A
+// row here takes the form the dense launch would take for its length (tap_sum), so that a row of a ragged batch comes
+// out bit for bit as it does alone.  In reversed time logical step t lives at memory position n - 1 - t, so in memory
+// terms out[m] = act(bias + sum_k w[k] x[m + (W-1) - k]) with x[>= n] = 0.  Thread = 4 consecutive outputs as in
+// fwd_vec_kernel; VEC: 4-element aligned rows (vec_rows), else element-wise access.  Every input element is taken
+// through a select on its column, so what x holds past n is dropped whatever it is.
+template <int W>
+__device__ inline float tap_sum(float acc, const float* wk, const float* xs, bool fused) {   // xs[k]: the input of tap k
+    if (fused) {
+#pragma unroll
+        for (int k = 0; k < W; ++k) acc = fmaf(wk[k], xs[k], acc);
+    } else {
+#pragma unroll
+        for (int k = 0; k < W; ++k) acc = __fadd_rn(acc, __fmul_rn(wk[k], xs[k]));   // never contracted
+    }
+    return acc;
+}
+
+template <typename T, bool VEC>
+__device__ inline void ld4n(const T* row, int t, int n, float* v) {   // x[t .. t+3], 0 outside [0, n)
+    if (VEC) {
+        ld4z<T>(row, t, n, v);
+    } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = (t + i >= 0 && t + i < n) ? io<T>::ld(&row[t + i]) : 0.f;
+    }
+}
+
+template <typename T, int W, bool SILU, bool HAS_BIAS, bool VEC>
+__global__ __launch_bounds__(THREADS) void fwd_len_kernel(int D, int L, const T* __restrict__ x, int64_t x_bs,
+                                                          int64_t x_ds, const int32_t* __restrict__ lengths,
+                                                          const float* __restrict__ w,
+                                                          const float* __restrict__ bias, T* __restrict__ out,
+                                                          int64_t o_bs, int64_t o_ds, int rev) {
+    const int row = blockIdx.x;
+    const int b = row / D, d = row % D;
+    const int n = min(max((int)lengths[b], 0), L);
+    const T* xr = x + b * x_bs + (int64_t)d * x_ds;
+    T* orow = out + b * o_bs + (int64_t)d * o_ds;
+    float wk[W];
+#pragma unroll
+    for (int k = 0; k < W; ++k) wk[k] = w[d * W + k];
+    const float bv = HAS_BIAS ? bias[d] : 0.f;
+    const bool fused = VEC && n > SHORT_L;        // the dense launch's choice for a row of n columns (launch_fwd)
+    for (int t = threadIdx.x * 4; t < L; t += THREADS * 4) {
+        float o[4] = {0.f, 0.f, 0.f, 0.f};
+        if (t < n) {
+            float e[8], xs[W];
+            if (!rev) {                           // e[i] = x[t - 4 + i]
+                ld4n<T, VEC>(xr, t - 4, n, e);
+                ld4n<T, VEC>(xr, t, n, e + 4);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+#pragma unroll
+                    for (int k = 0; k < W; ++k) xs[k] = e[4 + j - (W - 1) + k];
+                    const float acc = tap_sum<W>(bv, wk, xs, fused);
+                    o[j] = SILU ? siluf_(acc) : acc;
+                }
+            } else {                              // e[i] = x[t + i]
+                ld4n<T, VEC>(xr, t, n, e);
+                ld4n<T, VEC>(xr, t + 4, n, e + 4);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+#pragma unroll
+                    for (int k = 0; k < W; ++k) xs[k] = e[j + (W - 1) - k];
+                    const float acc = tap_sum<W>(bv, wk, xs, fused);
+                    o[j] = SILU ? siluf_(acc) : acc;
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (t + j >= n) o[j] = 0.f;       // the row's padding inside its last 4-vector
+        }
+        if (VEC) {
+            st4<T>(orow, t, L, o);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (t + j < L) io<T>::st(&orow[t + j], o[j]);
+        }
+    }
+}
+
 // ---------------------------------------------------------------- carried left context (streaming inference)
 // The three forward paths again, continuing a row from a cached conv_state (b, d, W) = the row's last W inputs,
 // oldest first (bimamba.py:277,328-329): x[-j] = state[W - j].  One owner thread per row (thread 0 of the row's
@@ -735,6 +822,19 @@ void launch_fwd(int64_t batch, int64_t dim, int64_t seqlen, const T* x, int64_t 
 }
 
 template <typename T, int W, bool S, bool HB>
+void launch_fwd_len(int64_t batch, int64_t dim, int64_t seqlen, const T* x, int64_t x_bs, int64_t x_ds,
+                    const int32_t* lengths, const float* w, const float* bias, T* out, int64_t o_bs, int64_t o_ds,
+                    int rev, hipStream_t st) {
+    const int rows = (int)(batch * dim);
+    if (vec_rows<T>(x, x_bs, x_ds, seqlen, true) && vec_rows<T>(out, o_bs, o_ds, seqlen, false))
+        hipLaunchKernelGGL((fwd_len_kernel<T, W, S, HB, true>), dim3((unsigned)rows), dim3(THREADS), 0, st, (int)dim,
+                           (int)seqlen, x, x_bs, x_ds, lengths, w, bias, out, o_bs, o_ds, rev);
+    else
+        hipLaunchKernelGGL((fwd_len_kernel<T, W, S, HB, false>), dim3((unsigned)rows), dim3(THREADS), 0, st, (int)dim,
+                           (int)seqlen, x, x_bs, x_ds, lengths, w, bias, out, o_bs, o_ds, rev);
+}
+
+template <typename T, int W, bool S, bool HB>
 void launch_bwd(int64_t batch, int64_t dim, int64_t seqlen, const T* x, int64_t x_bs, int64_t x_ds, const float* w,
                 const float* bias, const T* dout, int64_t g_bs, int64_t g_ds, T* dx, int64_t dx_bs, int64_t dx_ds,
                 float* ws, int rev, int dx_acc, uint32_t* dx_max, hipStream_t st) {
@@ -807,6 +907,10 @@ struct Fwd {
     template <typename... A> static void run(A... a) { launch_fwd<T, W, S, HB>(a...); }
 };
 template <typename T, int W, bool S, bool HB>
+struct FwdLen {
+    template <typename... A> static void run(A... a) { launch_fwd_len<T, W, S, HB>(a...); }
+};
+template <typename T, int W, bool S, bool HB>
 struct Bwd {
     template <typename... A> static void run(A... a) { launch_bwd<T, W, S, HB>(a...); }
 };
@@ -855,6 +959,20 @@ int cconv_fwd(int64_t batch, int64_t dim, int64_t seqlen, int64_t width, const T
     if (batch * dim > (1LL << 31) - 1) return AVSE_ESHAPE;
     const int rc = dispatch<Fwd, T>(width, silu != 0, bias != nullptr, batch, dim, seqlen, x, x_bs, x_ds, weight, bias,
                                     out, out_bs, out_ds, (int)reverse, (hipStream_t)stream);
+    if (rc != AVSE_OK) return rc;
+    AVSE_CHECK_LAUNCH();
+    return AVSE_OK;
+}
+
+template <typename T>
+int cconv_fwd_len(int64_t batch, int64_t dim, int64_t seqlen, int64_t width, const T* x, int64_t x_bs, int64_t x_ds,
+                  const int32_t* lengths, const float* weight, const float* bias, T* out, int64_t out_bs,
+                  int64_t out_ds, int32_t silu, int32_t reverse, avse_stream_t stream) {
+    if (!x || !lengths || !weight || !out) return AVSE_EINVAL;
+    if (batch <= 0 || dim <= 0 || seqlen <= 0 || width < 1 || width > MAXW) return AVSE_ESHAPE;
+    if (batch * dim > (1LL << 31) - 1 || seqlen > (1LL << 31) - 1 - 4 * THREADS) return AVSE_ESHAPE;
+    const int rc = dispatch<FwdLen, T>(width, silu != 0, bias != nullptr, batch, dim, seqlen, x, x_bs, x_ds, lengths,
+                                       weight, bias, out, out_bs, out_ds, (int)reverse, (hipStream_t)stream);
     if (rc != AVSE_OK) return rc;
     AVSE_CHECK_LAUNCH();
     return AVSE_OK;
@@ -949,6 +1067,21 @@ int avse_cconv_fwd_bf16(int64_t batch, int64_t dim, int64_t seqlen, int64_t widt
                         int64_t out_ds, int32_t silu, int32_t reverse, avse_stream_t stream) {
     return cconv_fwd<bf16_t>(batch, dim, seqlen, width, (const bf16_t*)x, x_bs, x_ds, weight, bias, (bf16_t*)out,
                              out_bs, out_ds, silu, reverse, stream);
+}
+
+int avse_cconv_fwd_len(int64_t batch, int64_t dim, int64_t seqlen, int64_t width, const float* x, int64_t x_bs,
+                       int64_t x_ds, const int32_t* lengths, const float* weight, const float* bias, float* out,
+                       int64_t out_bs, int64_t out_ds, int32_t silu, int32_t reverse, avse_stream_t stream) {
+    return cconv_fwd_len<float>(batch, dim, seqlen, width, x, x_bs, x_ds, lengths, weight, bias, out, out_bs, out_ds,
+                                silu, reverse, stream);
+}
+
+int avse_cconv_fwd_len_bf16(int64_t batch, int64_t dim, int64_t seqlen, int64_t width, const uint16_t* x, int64_t x_bs,
+                            int64_t x_ds, const int32_t* lengths, const float* weight, const float* bias,
+                            uint16_t* out, int64_t out_bs, int64_t out_ds, int32_t silu, int32_t reverse,
+                            avse_stream_t stream) {
+    return cconv_fwd_len<bf16_t>(batch, dim, seqlen, width, (const bf16_t*)x, x_bs, x_ds, lengths, weight, bias,
+                                 (bf16_t*)out, out_bs, out_ds, silu, reverse, stream);
 }
 
 int avse_cconv_bwd_bf16(int64_t batch, int64_t dim, int64_t seqlen, int64_t width, const uint16_t* x, int64_t x_bs,

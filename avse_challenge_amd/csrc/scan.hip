@@ -514,6 +514,180 @@ __global__ __launch_bounds__(THREADS) void fwd_state_kernel(avse_scan_fwd_args a
             make_float4(h2[0].x, h2[0].y, h2[1].x, h2[1].y);
 }
 
+// ------------------------------------------------------------------------------- forward of a ragged batch
+// avse_scan_fwd_len (inference on a zero-padded batch of rows of different lengths): fwd_kernel's second sibling, kept
+// apart for the same reason.  Same staging, recurrence and flush, run over the row's own length L = clamp(lengths[b], 0,
+// seqlen) instead of seqlen: with reverse set, logical step t lives at memory position L - 1 - t, chunks past L are
+// neither loaded nor stepped, and per element the arithmetic is fwd_kernel's on the row cropped to L columns.
+// Differences: no checkpoints are written, and the outputs' columns L .. seqlen - 1 are stored as +0 (out_z's are
+// left as they are with out_z_accumulate: the first direction wrote its zeros there).  What the inputs hold past L is
+// either not loaded or dropped by the selects of the staging and by the flush's store mask.
+template <typename Tin, bool HAS_Z, bool HAS_D, bool HAS_BIAS, bool SOFTPLUS>
+__global__ __launch_bounds__(THREADS) void fwd_len_kernel(avse_scan_fwd_args a, int nblk_d,
+                                                          const int32_t* __restrict__ lengths) {
+    __shared__ __attribute__((aligned(16))) float s_ud[CPB * UD_STRIDE];
+    __shared__ __attribute__((aligned(16))) float s_bc[TC * BC_STRIDE];
+    __shared__ float2 s_par[CPB];                      // (delta_bias, D) per row of the block
+
+    const int bid = xcd_remap(blockIdx.x, gridDim.x);
+    const int b = bid / nblk_d, d0 = (bid % nblk_d) * CPB;
+    const int D = (int)a.dim, Lmax = (int)a.seqlen;
+    const int L = min(max((int)lengths[b], 0), Lmax);  // the row's own length (uniform over the workgroup)
+    const bool rev = a.reverse != 0;
+    const Lane id = lane_ids();
+    const int d = d0 + id.c;
+    const bool dvalid = d < D;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (threadIdx.x < CPB) {
+        const int r = d0 + (int)threadIdx.x;
+        s_par[threadIdx.x] = make_float2((HAS_BIAS && r < D) ? a.delta_bias[r] : 0.f, (HAS_D && r < D) ? a.D[r] : 0.f);
+    }
+
+    // the lane's 4 states as 2 packed pairs: every state update is v_pk_mul / v_pk_fma on pairs
+    f2_t A2v[NS / 2], h2[NS / 2];
+#pragma unroll
+    for (int p = 0; p < NS / 2; ++p) {
+        const int j = id.g * NS + 2 * p;
+        A2v[p] = dvalid ? f2_t{a.A[(int64_t)d * NSTATE + j], a.A[(int64_t)d * NSTATE + j + 1]} * AVSE_LOG2E : f2_t{0.f, 0.f};
+        h2[p] = f2_t{0.f, 0.f};
+    }
+
+    const Tin* u = (const Tin*)a.u;
+    const Tin* dl = (const Tin*)a.delta;
+    const Tin* z = (const Tin*)a.z;
+    const int nck = (L + TC - 1) / TC;                 // 0 for an empty row: nothing is loaded
+
+    const int nrow = min(CPB, D - d0);
+    RowRegs<Tin> ru, rd;
+    BCRegs<Tin> rbc;
+    if (nck > 0) {
+        ru.load(u, a.u_bs, a.u_ds, b, d0, D, 0, min(TC, L), L, rev);
+        rd.load(dl, a.delta_bs, a.delta_ds, b, d0, D, 0, min(TC, L), L, rev);
+        rbc.load((const Tin*)a.B, a.B_bs, a.B_ns, (const Tin*)a.C, a.C_bs, a.C_ns, b, 0, min(TC, L), L, rev);
+    }
+    __syncthreads();                                   // s_par
+    float du_keep[RPT];                                // D u of the thread's staged elements, added at the flush
+    float zmax = 0.f;                                  // out_z_max: running max |out_z| of the thread's elements
+
+    for (int k = 0; k < nck; ++k) {
+        const int t0 = k * TC, tn = min(TC, L - t0);
+        // registers -> LDS (chunk k)
+        if (tn == TC && nrow == CPB)
+            store_fwd<Tin, SOFTPLUS, HAS_BIAS, HAS_D, true>(s_ud, ru, rd, s_par, du_keep, tn, nrow);
+        else
+            store_fwd<Tin, SOFTPLUS, HAS_BIAS, HAS_D, false>(s_ud, ru, rd, s_par, du_keep, tn, nrow);
+        rbc.store(s_bc, tn);
+        __syncthreads();
+        // prefetch chunk k + 1 while chunk k computes
+        if (k + 1 < nck) {
+            const int t1 = t0 + TC, tn1 = min(TC, L - t1);
+            ru.load(u, a.u_bs, a.u_ds, b, d0, D, t1, tn1, L, rev);
+            rd.load(dl, a.delta_bs, a.delta_ds, b, d0, D, t1, tn1, L, rev);
+            rbc.load((const Tin*)a.B, a.B_bs, a.B_ns, (const Tin*)a.C, a.C_bs, a.C_ns, b, t1, tn1, L, rev);
+        }
+
+        float* my_ud = &s_ud[id.c * UD_STRIDE];
+        // 8 steps per iteration: the LDS reads of all 8 issue together and the 8 cross-lane
+        // y reductions (DPP) are independent, so one wave per SIMD still keeps its pipes busy.
+        constexpr int U = 8;
+        auto steps = [&](int t, auto UNR) {
+            constexpr int NU = decltype(UNR)::value;
+            float yv[NU];
+#pragma unroll
+            for (int q = 0; q < NU; ++q) {
+                const float2 ud = *reinterpret_cast<const float2*>(&my_ud[2 * (t + q)]);   // (dt u, dt)
+                const float4 bq = *reinterpret_cast<const float4*>(&s_bc[(t + q) * BC_STRIDE + id.g * NS]);
+                const float4 cq = *reinterpret_cast<const float4*>(&s_bc[(t + q) * BC_STRIDE + NSTATE + id.g * NS]);
+                const f2_t bp[2] = {f2_t{bq.x, bq.y}, f2_t{bq.z, bq.w}};
+                const f2_t cp[2] = {f2_t{cq.x, cq.y}, f2_t{cq.z, cq.w}};
+                const f2_t dt2 = f2_t{ud.y, ud.y}, dtu2 = f2_t{ud.x, ud.x};
+                f2_t y2 = f2_t{0.f, 0.f};
+#pragma unroll
+                for (int p = 0; p < NS / 2; ++p) {
+                    h2[p] = exp2_2(dt2 * A2v[p]) * h2[p] + dtu2 * bp[p];
+                    y2 += h2[p] * cp[p];
+                }
+                yv[q] = y2.x + y2.y;
+            }
+#pragma unroll
+            for (int q = 0; q < NU; ++q) yv[q] = group_sum<G>(yv[q]);
+            // every lane of the channel's quad holds the same sum and writes it to the same LDS word:
+            // no exec-mask branch per step, so the NU reductions and stores schedule together
+#pragma unroll
+            for (int q = 0; q < NU; ++q) my_ud[2 * (t + q)] = yv[q];   // dt u slot <- y (D u added at the flush)
+        };
+        // always the full 64 steps: the staged tail of the row's last chunk is zero (dt = 0, u = 0, B = C = 0), which
+        // leaves h unchanged, so no step needs a bounds test
+#pragma unroll 1
+        for (int q32 = 0; q32 < TC / 32; ++q32) {
+            steps(q32 * 32, std::integral_constant<int, U>());
+            steps(q32 * 32 + U, std::integral_constant<int, U>());
+            steps(q32 * 32 + 2 * U, std::integral_constant<int, U>());
+            steps(q32 * 32 + 3 * U, std::integral_constant<int, U>());
+        }
+        RowRegs<Tin> rz;       // this chunk's z for the gate, issued before the barrier wait
+        if (HAS_Z) rz.load(z, a.z_bs, a.z_ds, b, d0, D, t0, tn, L, rev);
+        RowRegs<Tin> racc;     // out_z_accumulate: the other direction's gated output, added at the flush
+        if (HAS_Z && a.out_z_accumulate)
+            racc.load((const Tin*)a.out_z, a.out_z_bs, a.out_z_ds, b, d0, D, t0, tn, L, rev);
+        __syncthreads();
+        // flush chunk k outputs (lane = time column, rows wave + 4i): buffer stores, row step in soffset
+        {
+            const auto ro = make_rsrc((Tin*)a.out + b * a.out_bs + (int64_t)d0 * a.out_ds,
+                                      (int64_t)(nrow - 1) * a.out_ds + L);
+            const int vo = wave * (int)a.out_ds + tpos(t0 + lane, L, rev);
+            // rows past D need no test: their offsets lie beyond the resource's range, whose stores the hardware
+            // drops; steps past L do (inside the range they would land in the row padding), one exec mask for all
+            float outv[RPT];
+#pragma unroll
+            for (int i = 0; i < RPT; ++i) outv[i] = s_ud[(wave + 4 * i) * UD_STRIDE + 2 * lane] + du_keep[i];
+            if (a.out && lane < tn) {
+#pragma unroll
+                for (int i = 0; i < RPT; ++i) bufst<Tin>::st(ro, vo, 4 * i * (int)a.out_ds, outv[i]);
+            }
+            if (HAS_Z) {
+                const auto rz_ = make_rsrc((Tin*)a.out_z + b * a.out_z_bs + (int64_t)d0 * a.out_z_ds,
+                                           (int64_t)(nrow - 1) * a.out_z_ds + L);
+                const int vz = wave * (int)a.out_z_ds + tpos(t0 + lane, L, rev);
+#pragma unroll
+                for (int i = 0; i < RPT; ++i) outv[i] *= siluf_(rz.at(i));   // 16 independent gates (ILP)
+                if (a.out_z_accumulate) {
+#pragma unroll
+                    for (int i = 0; i < RPT; ++i) outv[i] += racc.at(i);
+                }
+                if (lane < tn) {
+#pragma unroll
+                    for (int i = 0; i < RPT; ++i) bufst<Tin>::st(rz_, vz, 4 * i * (int)a.out_z_ds, outv[i]);
+                    if (a.out_z_max) {
+#pragma unroll
+                        for (int i = 0; i < RPT; ++i)
+                            if (wave + 4 * i < nrow) zmax = fmaxf(zmax, fabsf(outv[i]));
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
+    // the row's padding: +0 at columns L .. seqlen - 1 of the block's rows (lane = column, rows wave + 4i as above)
+    {
+        const bool zo = a.out != nullptr, zz = HAS_Z && !a.out_z_accumulate;
+        const auto ro = make_rsrc((Tin*)a.out + b * a.out_bs + (int64_t)d0 * a.out_ds,
+                                  zo ? (int64_t)(nrow - 1) * a.out_ds + Lmax : 0);
+        const auto rz_ = make_rsrc((Tin*)a.out_z + b * a.out_z_bs + (int64_t)d0 * a.out_z_ds,
+                                   zz ? (int64_t)(nrow - 1) * a.out_z_ds + Lmax : 0);
+        for (int c = L + lane; c < Lmax; c += 64) {
+#pragma unroll
+            for (int i = 0; i < RPT; ++i) {
+                if (wave + 4 * i < nrow) {
+                    if (zo) bufst<Tin>::st(ro, wave * (int)a.out_ds + c, 4 * i * (int)a.out_ds, 0.f);
+                    if (zz) bufst<Tin>::st(rz_, wave * (int)a.out_z_ds + c, 4 * i * (int)a.out_z_ds, 0.f);
+                }
+            }
+        }
+    }
+    if (HAS_Z && a.out_z_max) block_absmax_to(zmax, a.out_z_max);     // a.out_z_max: uniform over the grid
+}
+
 
 // ------------------------------------------------------------------------------- backward
 // Sum of 8 values over the 16 channel lanes (lane bits 2..5) of a wave without selects: a
@@ -973,6 +1147,17 @@ static void launch_fwd_state(const avse_scan_fwd_args& a, const CarriedState& hs
                            nblk_d, hs);
 }
 
+template <typename Tin, bool HAS_Z, bool HAS_D, bool HAS_BIAS>
+static void launch_fwd_len(const avse_scan_fwd_args& a, const int32_t* lengths, int nblk_d, int nblocks,
+                           hipStream_t st) {
+    if (a.delta_softplus == 1)
+        hipLaunchKernelGGL((fwd_len_kernel<Tin, HAS_Z, HAS_D, HAS_BIAS, true>), dim3(nblocks), dim3(THREADS), 0, st, a,
+                           nblk_d, lengths);
+    else
+        hipLaunchKernelGGL((fwd_len_kernel<Tin, HAS_Z, HAS_D, HAS_BIAS, false>), dim3(nblocks), dim3(THREADS), 0, st, a,
+                           nblk_d, lengths);
+}
+
 // ------------------------------------------------------------------------------- single step
 // selective_state_update (bimamba.py:352-358) with the scan's lane mapping: 4 adjacent lanes per channel, 4 states
 // each (one 16-B state load and store per lane), y reduced over the quad by DPP.  Launch-bound at every real size.
@@ -1123,6 +1308,36 @@ int avse_scan_fwd_state(const avse_scan_fwd_state_args* as, avse_stream_t stream
     hipStream_t st = (hipStream_t)stream;
     if (a->in_dtype == AVSE_F32) AVSE_DISPATCH_FLAGS_STATE(float, (*a), hs, nblk_d, nblocks, st);
     else AVSE_DISPATCH_FLAGS_STATE(bf16_t, (*a), hs, nblk_d, nblocks, st);
+    AVSE_CHECK_LAUNCH();
+    return AVSE_OK;
+}
+
+#define AVSE_DISPATCH_FLAGS_LEN(T, ARGS, LEN, ...)                                                  \
+    do {                                                                                           \
+        const bool hz = ARGS.z != nullptr, hd = ARGS.D != nullptr, hb = ARGS.delta_bias != nullptr; \
+        if (hz && hd && hb) launch_fwd_len<T, true, true, true>(ARGS, LEN, __VA_ARGS__);           \
+        else if (hz && hd) launch_fwd_len<T, true, true, false>(ARGS, LEN, __VA_ARGS__);           \
+        else if (hz && hb) launch_fwd_len<T, true, false, true>(ARGS, LEN, __VA_ARGS__);           \
+        else if (hz) launch_fwd_len<T, true, false, false>(ARGS, LEN, __VA_ARGS__);                \
+        else if (hd && hb) launch_fwd_len<T, false, true, true>(ARGS, LEN, __VA_ARGS__);           \
+        else if (hd) launch_fwd_len<T, false, true, false>(ARGS, LEN, __VA_ARGS__);                \
+        else if (hb) launch_fwd_len<T, false, false, true>(ARGS, LEN, __VA_ARGS__);                \
+        else launch_fwd_len<T, false, false, false>(ARGS, LEN, __VA_ARGS__);                       \
+    } while (0)
+
+int avse_scan_fwd_len(const avse_scan_fwd_args* a, const int32_t* lengths, avse_stream_t stream) {
+    if (!a || !lengths || !a->u || !a->delta || !a->A || !a->B || !a->C) return AVSE_EINVAL;   // x may be NULL: unused
+    if (a->z ? !a->out_z : !a->out) return AVSE_EINVAL;
+    if (!a->z && (a->out_z_accumulate || a->out_z_max)) return AVSE_EINVAL;
+    int rc = check_mode(a->delta_softplus, a->delta_bias);
+    if (rc) return rc;
+    rc = check_common(a->batch, a->dim, a->seqlen, a->dstate, a->in_dtype);
+    if (rc) return rc;
+    const int nblk_d = (int)((a->dim + CPB - 1) / CPB);
+    const int nblocks = (int)(a->batch * nblk_d);
+    hipStream_t st = (hipStream_t)stream;
+    if (a->in_dtype == AVSE_F32) AVSE_DISPATCH_FLAGS_LEN(float, (*a), lengths, nblk_d, nblocks, st);
+    else AVSE_DISPATCH_FLAGS_LEN(bf16_t, (*a), lengths, nblk_d, nblocks, st);
     AVSE_CHECK_LAUNCH();
     return AVSE_OK;
 }

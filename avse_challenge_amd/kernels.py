@@ -139,10 +139,28 @@ def _ssm_state_arg(t, b, d, dev, what):
     return t
 
 
+def _row_lengths(lengths, batch, device, what):
+    """The int32 device tensor of a ragged batch's `batch` row lengths (avse_scan_fwd_len, avse_cconv_fwd_len): an int32
+    tensor on the device is taken as it is, a sequence is uploaded.  The kernels clamp each value to [0, seqlen], so no
+    value is read back here."""
+    if not torch.is_tensor(lengths):
+        lengths = torch.tensor([int(v) for v in lengths], dtype=torch.int32, device=device)
+    if lengths.dtype != torch.int32 or lengths.device != device or tuple(lengths.shape) != (batch,) \
+            or not lengths.is_contiguous():
+        raise ValueError(f"{what}: lengths must be {batch} int32 values on {device} (or a sequence), got "
+                         f"{tuple(lengths.shape)} {lengths.dtype} on {lengths.device}")
+    return lengths
+
+
 def selective_scan_fwd(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, reverse=False,
                        return_out=True, out_z_acc=None, out_z_max=None, initial_state=None, return_last_state=False,
-                       checkpoints=True):
+                       checkpoints=True, lengths=None):
     """Returns (out, x, out_z|None) — the selective_scan_cuda.fwd contract.
+    lengths (inference on a zero-padded ragged batch, avse_scan_fwd_len): b row lengths, an int32 device tensor or a
+    sequence.  Row i is scanned over its first clamp(lengths[i], 0, l) columns only, exactly as the dense call scans
+    the cropped row (reverse=True starts at the row's own last column); what the inputs hold past them is not used,
+    the outputs are 0 there (out_z_acc keeps its values there) and out_z_max covers the valid columns.  No checkpoints
+    are written (x is returned as None: no backward can follow); not together with the carried state below.
     Carried state (causal streaming inference, avse_scan_fwd_state; forward time order only): initial_state, an fp32
     (b, d, 16) tensor (the reference's ssm_state layout) the scan starts from instead of zeros; return_last_state,
     True or an fp32 (b, d, 16) tensor to write (it may be initial_state itself: in-place update): the state after the
@@ -170,7 +188,12 @@ def selective_scan_fwd(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta
     nck = L.avse_scan_n_chunks(l)
     if not return_out and z is None:
         raise RuntimeError("return_out=False needs z (the gated output is then the only result)")
-    stateful = initial_state is not None or return_last_state is not False or not checkpoints
+    if lengths is not None:
+        if initial_state is not None or return_last_state is not False:
+            raise RuntimeError("selective_scan_fwd: lengths cannot be combined with a carried state")
+        lengths = _row_lengths(lengths, b, u.device, "selective_scan_fwd")
+        checkpoints = False
+    stateful = lengths is None and (initial_state is not None or return_last_state is not False or not checkpoints)
     if stateful and (reverse or out_z_acc is not None or out_z_max is not None):
         raise RuntimeError("selective_scan_fwd: carried state runs forwards in time, without out_z_acc / out_z_max")
     out = _bdl_empty(b, d, l, dt, u.device) if return_out else None
@@ -214,6 +237,11 @@ def selective_scan_fwd(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta
         check(L.avse_scan_fwd_state(sa, stream_ptr(u.device)), "avse_scan_fwd_state")
         _tap_end(tap)
         return (out, x, out_z, last) if return_last_state is not False else (out, x, out_z)
+    if lengths is not None:
+        tap = _tap_begin("avse_scan_fwd_len", u.device)
+        check(L.avse_scan_fwd_len(a, ptr(lengths), stream_ptr(u.device)), "avse_scan_fwd_len")
+        _tap_end(tap)
+        return out, None, out_z
     tap = _tap_begin("avse_scan_fwd", u.device)
     check(L.avse_scan_fwd(a, stream_ptr(u.device)), "avse_scan_fwd")
     _tap_end(tap)
@@ -352,8 +380,12 @@ def _conv_state_arg(t, b, d, w, dt, dev):
     return t
 
 
-def causal_conv1d_fwd(x, weight, bias=None, silu=False, reverse=False, conv_state=None):
+def causal_conv1d_fwd(x, weight, bias=None, silu=False, reverse=False, conv_state=None, lengths=None):
     """out = act(depthwise causal conv(x)) in x's dtype (fp32 or bf16; fp32 weights and arithmetic).
+    lengths (inference on a zero-padded ragged batch, avse_cconv_fwd_len): b row lengths, an int32 device tensor or a
+    sequence; row i is convolved over its first clamp(lengths[i], 0, l) columns exactly as the dense call convolves the
+    cropped row (reverse=True starts at the row's own last column), what x holds past them is not used and out is 0
+    there.  Not together with conv_state.
     conv_state (streaming inference): a (b, d, w) tensor of x's dtype holding the row's last w inputs, oldest first
     (the reference's conv_state, bimamba.py:277); the conv takes x[t < 0] from it and it is updated in place to the last
     w of concat(conv_state, x)."""
@@ -368,6 +400,15 @@ def causal_conv1d_fwd(x, weight, bias=None, silu=False, reverse=False, conv_stat
     b, d, l = x.shape
     w = weight.shape[1]
     out = _bdl_empty(b, d, l, dt, x.device)
+    if lengths is not None:
+        if conv_state is not None:
+            raise RuntimeError("causal_conv1d_fwd: lengths cannot be combined with a carried conv_state")
+        lengths = _row_lengths(lengths, b, x.device, "causal_conv1d_fwd")
+        fn = _lib.lib().avse_cconv_fwd_len if dt == torch.float32 else _lib.lib().avse_cconv_fwd_len_bf16
+        check(fn(b, d, l, w, ptr(x), x.stride(0), x.stride(1), ptr(lengths), ptr(weight), ptr(bias), ptr(out),
+                 out.stride(0), out.stride(1), int(bool(silu)), int(bool(reverse)), stream_ptr(x.device)),
+              "avse_cconv_fwd_len")
+        return out
     if conv_state is not None:
         if reverse:
             raise RuntimeError("causal_conv1d_fwd: a carried conv_state runs forwards in time")

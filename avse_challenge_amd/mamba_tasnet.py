@@ -188,19 +188,21 @@ def _delta(dt_proj_w, x_rows, dt_bias):
     return _wbmm(dt_proj_w, x_rows), dt_bias, True
 
 
-def _dir_fwd(xz, conv_w, conv_b, x_proj_w, dt_proj_w, A, D, dt_bias, reverse, acc=None, out_max=None):
+def _dir_fwd(xz, conv_w, conv_b, x_proj_w, dt_proj_w, A, D, dt_bias, reverse, acc=None, out_max=None, lengths=None):
     """One BiMamba direction's forward (MambaInnerNoOutProj): -> (out_z, tensors to save).  acc: a tensor the gated
-    output is added to in place (the scan's flush) and returned as out_z; out_max: a zeroed word for max |out_z|."""
+    output is added to in place (the scan's flush) and returned as out_z; out_max: a zeroed word for max |out_z|.
+    lengths (inference on a ragged batch): the rows' frame counts as an int32 device tensor; the conv and the scan then
+    run over each row's own frames (reverse starts at its own last frame) and write 0 past them, no checkpoints."""
     R = dt_proj_w.shape[1]
     x, z = xz.chunk(2, dim=1)
-    conv_out = K.causal_conv1d_fwd(x, conv_w, conv_b, silu=True, reverse=reverse)     # (b, d, l)
+    conv_out = K.causal_conv1d_fwd(x, conv_w, conv_b, silu=True, reverse=reverse, lengths=lengths)     # (b, d, l)
     x_dblT = _wbmm(x_proj_w, conv_out)                                       # (b, R + 2n, l)
     delta, bias, mode = _delta(dt_proj_w, x_dblT[:, :R], dt_bias)             # (b, d, l)
     Bm, Cm = x_dblT[:, R:R + NSTATE], x_dblT[:, R + NSTATE:]                 # (b, n, l) views
     # the pre-gate `out` is neither written nor saved (the reference saves it, :212): the scan
     # backward recomputes y + D u per step anyway, so it only cost HBM traffic and memory
     _, xck, out_z = K.selective_scan_fwd(conv_out, delta, A, Bm, Cm, D, z, bias, mode, reverse=reverse,
-                                         return_out=False, out_z_acc=acc, out_z_max=out_max)
+                                         return_out=False, out_z_acc=acc, out_z_max=out_max, lengths=lengths)
     return out_z, (xz, conv_w, conv_b, x_dblT, x_proj_w, dt_proj_w, A, D, dt_bias, xck)
 
 
@@ -663,6 +665,25 @@ class BiMambaV2(_StatefulMixer, nn.Module):
         # == out_proj(0.5*out + 0.5*out_b.flip(-1)) of bimamba.py:253, flip-free, one batched GEMM
         return _BiOutProj.apply(f, bk, self.out_proj.weight)
 
+    @torch.no_grad()
+    def forward_ragged(self, h, frame_lengths):
+        """forward() for a zero-padded batch whose row b holds frame_lengths[b] frames (an int32 device tensor):
+        (b, l, d_model) -> (b, l, d_model), inference only.  Both directions run over each row's own frames through the
+        length-aware conv and scan (the time-reversed one starts at the row's own last frame, not in the padding), with
+        BiMambaSerial's in-place direction sum and producer-side max; the sum is 0 past a row's frames, so the
+        out_proj's output is 0 there too.  The projections act per frame."""
+        xz = _InProj.apply(h, self.in_proj.weight)
+        mx = torch.zeros(1, device=xz.device, dtype=torch.int32) if xz.dtype == torch.float32 else None
+        f, _ = _dir_fwd(xz, self.conv1d.weight, self.conv1d.bias, self.x_proj.weight, self.dt_proj.weight,
+                        -torch.exp(self.A_log.float()), self.D.float(), self.dt_proj.bias.float(), False,
+                        lengths=frame_lengths)
+        y, _ = _dir_fwd(xz, self.conv1d_b.weight, self.conv1d_b.bias, self.x_proj_b.weight, self.dt_proj_b.weight,
+                        -torch.exp(self.A_b_log.float()), self.D_b.float(), self.dt_proj_b.bias.float(), True, acc=f,
+                        out_max=mx, lengths=frame_lengths)
+        if mx is not None:
+            K._set_absmax(y, mx)
+        return _BiOutProj.apply(y, None, self.out_proj.weight)
+
 
 class Block(nn.Module):
     def __init__(self, d_model, mixer, eps=1e-5):
@@ -702,6 +723,17 @@ class MambaBlocksSequential(nn.Module):
         h, res = x, None
         for layer in self.layers:
             h, res = layer(h, res, inference_params)
+        return AddRMSNorm.apply(h, res, self.norm_f.weight, self.norm_f.eps)[0]
+
+    @torch.no_grad()
+    def forward_ragged(self, x, frame_lengths):
+        """forward() for a zero-padded ragged batch (frame_lengths: int32 device tensor, made once per forward).  The
+        norms act per frame; the bidirectional mixers take the lengths, the causal ones never look ahead into the
+        padding and run as they are."""
+        h, res = x, None
+        for layer in self.layers:
+            y, res = AddRMSNorm.apply(h, res, layer.norm.weight, layer.norm.eps, True)
+            h = layer.mixer.forward_ragged(y, frame_lengths) if self.bidirectional else layer.mixer(y)
         return AddRMSNorm.apply(h, res, self.norm_f.weight, self.norm_f.eps)[0]
 
 
@@ -745,6 +777,14 @@ class MaskNet(nn.Module):
         Bn, L, D = x.shape
         h = self.bottleneck_conv1x1(self.layer_norm(x))
         h = self.mamba_net(h) if inference_params is None else self.mamba_net(h, inference_params)
+        y = self.mask_conv1x1(h)
+        return F.relu(y.reshape(Bn, L, self.n_spk, D).permute(2, 0, 3, 1))
+
+    @torch.no_grad()
+    def forward_ragged(self, mixture_w, frame_lengths):     # forward() with the Mamba blocks' length-aware path
+        x = mixture_w.permute(0, 2, 1)
+        Bn, L, D = x.shape
+        h = self.mamba_net.forward_ragged(self.bottleneck_conv1x1(self.layer_norm(x)), frame_lengths)
         y = self.mask_conv1x1(h)
         return F.relu(y.reshape(Bn, L, self.n_spk, D).permute(2, 0, 3, 1))
 
@@ -795,6 +835,64 @@ class MambaTasNet(nn.Module):
         if T > est.shape[1]:
             return F.pad(est, (0, 0, 0, T - est.shape[1]))
         return est[:, :T, :]
+
+    @torch.no_grad()
+    def forward_ragged(self, mix, lengths):
+        """forward() for a batch of mixtures of different lengths in one pass (inference, fp32): mix (B, T_max) holds
+        utterance b in its first lengths[b] samples -> (B, T_max, n_spk) whose row b holds forward(mix[b:b+1,
+        :lengths[b]]) in its first lengths[b] samples and 0 after them.  What mix holds past an utterance is not used.
+
+        Utterance b has L_b = (T_b - k) // hop + 1 encoder frames.  Everything in the model acts per frame except the
+        BiMamba blocks (whose time-reversed direction would start in the padding: BiMambaV2.forward_ragged) and the
+        decoder's overlap-add (the padded frame L_b would reach into the last hop samples of the utterance: the masked
+        encoder output is set to 0 from frame L_b on).  Samples from (L_b - 1) hop + k on are 0, the F.pad of
+        train_wsj0mix.py:86-111: the utterance alone gives the same zeros when (T_b - k) % hop != 0."""
+        K._need_gpu(mix)
+        if _autocast_dtype() is not None:
+            raise RuntimeError("MambaTasNet.forward_ragged runs in fp32 (the bf16 autocast path is not built)")
+        k, hop = self.encoder.conv1d.kernel_size[0], self.encoder.conv1d.stride[0]
+        host = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
+        B, T = mix.shape
+        if len(host) != B or max(host) > T:
+            raise ValueError(f"forward_ragged: {B} lengths of at most {T} samples, got {host}")
+        if min(host) < k:
+            raise ValueError(f"forward_ragged: every utterance needs at least one encoder window of {k} samples, got "
+                             f"{min(host)}")
+        dev = mix.device
+        frames = [(t - k) // hop + 1 for t in host]
+        t_len = torch.tensor(host, device=dev)
+        f_len = torch.tensor(frames, dtype=torch.int32, device=dev)       # once per forward, for every layer
+        zero = mix.new_zeros(())
+        t_idx = torch.arange(T, device=dev)
+        mix = torch.where(t_idx[None, :] < t_len[:, None], mix, zero)     # a select: NaN in the padding is dropped
+        mix_w = self.encoder(mix)                                         # (B, N, L_max)
+        est_mask = self.masknet.forward_ragged(mix_w, f_len)
+        f_ok = torch.arange(mix_w.shape[-1], device=dev)[None, :] < f_len[:, None]            # (B, L_max)
+        sep_h = torch.where(f_ok[None, :, None, :], mix_w.unsqueeze(0) * est_mask, zero)
+        est = torch.stack([self.decoder(sep_h[i]) for i in range(self.num_spks)], dim=-1)
+        est = F.pad(est, (0, 0, 0, T - est.shape[1])) if T > est.shape[1] else est[:, :T, :]
+        t_ok = t_idx[None, :] < ((f_len.long() - 1) * hop + k)[:, None]
+        return torch.where(t_ok[:, :, None], est, zero)
+
+    def separate_batch(self, mixes, batch_size=8, max_pad_ratio=1.25):
+        """Separate a list of 1-D mixtures (tensors or arrays) of different lengths in length-planned padded batches
+        (avse4.plan_ragged_batches on the sample counts, one forward_ragged per batch): -> the list of (T_b, n_spk)
+        float32 arrays in input order, each what forward() returns for the utterance alone (to fp32 rounding)."""
+        import numpy as np
+
+        from .avse4 import plan_ragged_batches
+        dev = next(self.parameters()).device
+        waves = [np.asarray(m.detach().cpu() if torch.is_tensor(m) else m, dtype=np.float32).reshape(-1) for m in mixes]
+        out = [None] * len(waves)
+        for idx in plan_ragged_batches([w.shape[0] for w in waves], batch_size, max_pad_ratio):
+            tl = [waves[i].shape[0] for i in idx]
+            pad = np.zeros((len(idx), max(tl)), np.float32)
+            for r, i in enumerate(idx):
+                pad[r, :tl[r]] = waves[i]
+            est = self.forward_ragged(torch.from_numpy(pad).to(dev), tl).cpu().numpy()
+            for r, i in enumerate(idx):
+                out[i] = est[r, :tl[r]].copy()
+        return out
 
 
 class StreamingSeparator:

@@ -120,6 +120,20 @@ typedef struct {
 } avse_scan_fwd_state_args;
 int avse_scan_fwd_state(const avse_scan_fwd_state_args* a, avse_stream_t stream);
 
+/* Forward scan of a zero-padded batch of rows of different lengths (inference; no backward).  a: the fields of
+ * avse_scan_fwd; lengths: a->batch int32 values on the device.  With n_b = clamp(lengths[b], 0, seqlen), clamped in
+ * the kernel, row b is processed exactly as avse_scan_fwd processes the row cropped to n_b columns (the same arithmetic
+ * in the same order per element):
+ *   - with a->reverse, logical step t lives at memory position n_b - 1 - t, not at seqlen - 1 - t;
+ *   - what u, delta, B, C, z hold at columns >= n_b is never used (selects, so NaN or Inf there do not propagate);
+ *   - out, out_z are written as +0 at columns n_b .. seqlen - 1; with a->out_z_accumulate those columns of out_z are
+ *     left as they are (the first direction already wrote its zeros there);
+ *   - a->out_z_max covers the valid columns only; n_b = 0 gives an all-zero row;
+ *   - a->x (the checkpoints) may be NULL and is not written;
+ *   - chunks that lie wholly past n_b are neither loaded nor stepped: a short row's workgroup ends early.
+ * A NULL lengths or required pointer returns AVSE_EINVAL, bad shapes AVSE_ESHAPE, before any launch. */
+int avse_scan_fwd_len(const avse_scan_fwd_args* a, const int32_t* lengths, avse_stream_t stream);
+
 /* One recurrence step on a cached state: the selective_state_update(state, x, dt, A, B, C, D, z, dt_bias,
  * dt_softplus) contract of mamba-ssm 1.1.3 as called at bimamba.py:360-362, semantics bimamba.py:352-358:
  *   dt' = softplus(dt + dt_bias) (dt_softplus != 0; else dt + dt_bias); state = state exp(dt' A) + dt' x B;
@@ -186,6 +200,23 @@ int avse_cconv_fwd_bf16(int64_t batch, int64_t dim, int64_t seqlen, int64_t widt
                         const float* weight, const float* bias,
                         uint16_t* out, int64_t out_bs, int64_t out_ds, int32_t silu, int32_t reverse,
                         avse_stream_t stream);
+/* The forward for a zero-padded batch of rows of different lengths (inference; no backward): the arguments of
+ * avse_cconv_fwd / avse_cconv_fwd_bf16 plus lengths, batch int32 values on the device.  With n_b = clamp(lengths[b],
+ * 0, seqlen), clamped in the kernel, row b is processed exactly as the dense entry point processes the row cropped to
+ * n_b columns (bias + sum_k w[k] x, k ascending): with reverse, logical step t lives at memory position n_b - 1 - t;
+ * what x holds at columns >= n_b is never used (a select: NaN or Inf there do not propagate); out is written as +0 at
+ * columns n_b .. seqlen - 1, so n_b = 0 gives an all-zero row.  A NULL lengths, x, weight or out returns AVSE_EINVAL,
+ * bad shapes AVSE_ESHAPE, before any launch. */
+int avse_cconv_fwd_len(int64_t batch, int64_t dim, int64_t seqlen, int64_t width,
+                       const float* x, int64_t x_bs, int64_t x_ds, const int32_t* lengths,
+                       const float* weight, const float* bias,
+                       float* out, int64_t out_bs, int64_t out_ds, int32_t silu, int32_t reverse,
+                       avse_stream_t stream);
+int avse_cconv_fwd_len_bf16(int64_t batch, int64_t dim, int64_t seqlen, int64_t width,
+                            const uint16_t* x, int64_t x_bs, int64_t x_ds, const int32_t* lengths,
+                            const float* weight, const float* bias,
+                            uint16_t* out, int64_t out_bs, int64_t out_ds, int32_t silu, int32_t reverse,
+                            avse_stream_t stream);
 int avse_cconv_bwd_bf16(int64_t batch, int64_t dim, int64_t seqlen, int64_t width,
                         const uint16_t* x, int64_t x_bs, int64_t x_ds,
                         const float* weight, const float* bias,
