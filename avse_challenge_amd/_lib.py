@@ -214,6 +214,14 @@ SIGNATURES = {
     "avse_dwconv_gln_fwd_q_len": (c_i32, [c_i64] * 5 + [c_vp] * 6 + [c_f32] + [c_vp] * 3 + [c_i64] + [c_vp] * 4),
     "avse_dwconv_fwd_len": (c_i32, [c_i64] * 5 + [c_vp] * 5),
     "avse_upsample_linear_len": (c_i32, [c_i64] * 5 + [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp]),
+    # the avse1 ragged path: STFT / iSTFT, eval BatchNorm -> act and the lip-to-audio gather with per-sample lengths
+    "avse_stft_fwd_len": (c_i32, [c_i64, c_i64] + [c_vp] * 5),
+    "avse_istft_len": (c_i32, [c_i64] * 3 + [c_vp] * 6),
+    "avse_bnact_fwd_len": (c_i32, [c_i64] * 3 + [c_vp] * 3 + [c_i32, c_vp, c_i32, c_i32, c_f32] + [c_vp] * 6
+                           + [c_i64] * 4 + [c_i32, c_vp]),
+    "avse_bnact_fwd_q_len": (c_i32, [c_i64] * 3 + [c_vp] * 3 + [c_i32, c_vp, c_i32, c_i32, c_f32] + [c_vp] * 6
+                             + [c_i64] * 4 + [c_i32, c_vp]),
+    "avse_gather_nearest_len": (c_i32, [c_i64] * 4 + [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp]),
     "avse_lstm_padded_hidden": (c_i64, [c_i64]),
     "avse_lstm_group_size": (c_i64, [c_i64, c_i64]),
     "avse_lstm_group_workspace_bytes": (c_i64, [c_i64, c_i64]),

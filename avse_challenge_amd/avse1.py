@@ -118,6 +118,22 @@ class _TemporalBlock(nn.Module):          # utils/tcn.py:144-243 (dwpw=False, sy
         z = (y + x).contiguous()
         return self.relu(time_major_4d(z)).squeeze(3).transpose(1, 2)
 
+    def _half_ragged(self, x, conv, bn, act, lengths):
+        # the conv's bias and the BatchNorm shift make every row of the (T + pad) output non-zero; the length-aware pass
+        # writes 0 outside the window [pad / 2, pad / 2 + len_b) that the symmetric chomp maps onto [0, len_b)
+        y = time_conv1d(x, conv)
+        h = self.pad // 2
+        y = bn_act(time_major_4d(y), bn, act, lengths=lengths, t_off=h)
+        return y.squeeze(3).transpose(1, 2)[:, h:y.shape[2] - h]
+
+    def forward_ragged(self, x, lengths):
+        """forward (eval) for a zero-padded batch: x (B, T, C) exact 0 at t >= lengths[b]; so is the result (the
+        residual add and the PReLU keep zeros), and row b's valid part is forward(x[b:b+1, :lengths[b]])."""
+        y = self._half_ragged(x, self.conv1, self.batchnorm1, self.relu1, lengths)
+        y = self._half_ragged(y, self.conv2, self.batchnorm2, self.relu2, lengths)
+        z = (y + x).contiguous()
+        return self.relu(time_major_4d(z)).squeeze(3).transpose(1, 2)
+
 
 class _TCNTrunk(nn.Module):
     def __init__(self, c=512, levels=4, k=3, p_drop=0.2):
@@ -126,6 +142,11 @@ class _TCNTrunk(nn.Module):
 
     def forward(self, x):
         return self.network(x)
+
+    def forward_ragged(self, x, lengths):
+        for block in self.network:
+            x = block.forward_ragged(x, lengths)
+        return x
 
 
 class _TCN(nn.Module):                    # utils/nn.py:106-128 (extract_feats=True)
@@ -136,6 +157,14 @@ class _TCN(nn.Module):                    # utils/nn.py:106-128 (extract_feats=T
 
     def forward(self, x):                 # (B, T, 512) -> (B, T, 512); the reference's (B, 512, T) transposes are not made
         return self.tcn_trunk(x.contiguous())
+
+    def forward_ragged(self, x, lengths):
+        return self.tcn_trunk.forward_ragged(x.contiguous(), lengths)
+
+
+def _valid_steps(lengths, n):
+    """(B, n) bool: step t of sample b is one of its own (t < lengths[b])."""
+    return torch.arange(n, device=lengths.dev.device)[None, :] < lengths.dev[:, None]
 
 
 class VisualFeatNet(nn.Module):           # model.py:17-58
@@ -167,6 +196,31 @@ class VisualFeatNet(nn.Module):           # model.py:17-58
             x = x.transpose(1, 2).reshape(Bn * Tn, x.shape[1], x.shape[3], x.shape[4])
         x = self.trunk(x).view(Bn, Tn, -1)
         return self.tcn(x)
+
+    @torch.no_grad()
+    def forward_ragged(self, lips, vis_lengths):
+        """forward (eval) for a zero-padded batch of clips: lips (B, 3, Tvmax, H, W), uint8 or float, of which sample b's
+        first vis_lengths[b] frames count -> (B, Tvmax, 512) whose row b equals forward(lips[b:b+1, :, :vis_lengths[b]])
+        on its frames and is 0 after them.  The padding frames are selected to 0 before the Conv3d (its 5 time taps
+        then see the zero padding the clip alone has; bias-free, so NaN or 255 there never enter a product), the
+        per-frame trunk's output at them (that of an all-zero clip: finite, input-independent) is selected to 0 before
+        the TCN, and the TCN's BatchNorms write zeros themselves (csrc/bnact.hip apply_len_kernel)."""
+        if self.training:
+            raise RuntimeError("VisualFeatNet.forward_ragged is an inference path: call .eval() first")
+        Bn, Tn = lips.shape[0], lips.shape[2]
+        vl = K._lengths(vis_lengths, Bn, Tn, lips.device, "VisualFeatNet.forward_ragged")
+        valid = _valid_steps(vl, Tn)
+        lips = torch.where(valid[:, None, :, None, None], lips, lips.new_zeros(()))
+        conv, bn, act, pool = self.frontend3D
+        x = conv(lips)
+        if self.channels_last:
+            x = bn_act_pool_frames(x, bn, act, pool, bn_act)
+        else:
+            x = maxpool3d(bn_act(x, bn, act, lengths=vl), pool)
+            x = x.transpose(1, 2).reshape(Bn * Tn, x.shape[1], x.shape[3], x.shape[4])
+        x = self.trunk(x).view(Bn, Tn, -1)
+        x = torch.where(valid[:, :, None], x, x.new_zeros(()))
+        return self.tcn.forward_ragged(x, vl)
 
 
 class AudioFeatNet(nn.Module):            # model.py:181-267 (5 dilated 5x5 convs + 1x1 -> 4)
@@ -210,6 +264,29 @@ class AudioFeatNet(nn.Module):            # model.py:181-267 (5 dilated 5x5 conv
             else:
                 x = bn_act(conv(x), bn, "relu")
         x = bn_act(conv1x1_to4(x, self.convf), self.bn_last, "relu")     # csrc/convf.hip (HBM-streaming 1x1)
+        return x.permute(0, 2, 1, 3).reshape(-1, T, Fb * self.last_filter)
+
+    @torch.no_grad()
+    def forward_ragged(self, spec, frame_lengths):
+        """forward (eval) for a zero-padded batch of spectrograms: spec (B, 1, Tmax, F), exact 0 at frames
+        t >= frame_lengths[b] (kernels.stft with lengths) -> (B, Tmax, 4F) whose row b equals
+        forward(spec[b:b+1, :, :frame_lengths[b]]) on its frames and is 0 after them.  Every BatchNorm (bn0's shift on
+        the zero spectrum, the conv biases under bn1..bn5) writes exact 0 at the padding frames in its own pass, so
+        the dilated 5x5 convs read there the zeros their padding gives the utterance alone; bn1..bn4 write the split
+        layout of the split-fp16 conv that follows, scaled by the max over the valid frames."""
+        if self.training:
+            raise RuntimeError("AudioFeatNet.forward_ragged is an inference path: call .eval() first")
+        T, Fb = spec.shape[2], spec.shape[3]
+        fl = K._lengths(frame_lengths, spec.shape[0], T, spec.device, "AudioFeatNet.forward_ragged")
+        x = bn_act(spec.contiguous(), self.bn0, lengths=fl)
+        if self.channels_last:
+            x = x.contiguous(memory_format=torch.channels_last)
+        for i in range(1, self.num_conv + 1):
+            conv, bn = getattr(self, f"conv{i}"), getattr(self, f"bn{i}")
+            nxt = getattr(self, f"conv{i + 1}") if i < self.num_conv else None
+            y = conv(x)
+            x = bn_act(y, bn, "relu", q_fwd=nxt is not None and nxt.q_ok(y), lengths=fl)
+        x = bn_act(conv1x1_to4(x, self.convf), self.bn_last, "relu", lengths=fl)
         return x.permute(0, 2, 1, 3).reshape(-1, T, Fb * self.last_filter)
 
 
@@ -353,6 +430,106 @@ class AVNet(nn.Module):
             inp["lip_images"] = lip_images
         pred = self(inp)[:, 0]
         return K.istft(pred, spec, noisy_wave.shape[-1] if length is None else length)
+
+    # ---- ragged batches (inference): a batch of utterances of different lengths, each as enhance() gives it alone
+    @torch.no_grad()
+    def forward_ragged(self, inp, frame_lengths, vis_lengths=None):
+        """forward (eval, fp32) for a zero-padded batch: inp["noisy_audio_spec"] (B, 1, Tmax, F), exact 0 at frames
+        t >= frame_lengths[b]; inp["lip_images"] (B, 3, Tvmax, H, W) with vis_lengths[b] frames of sample b (not read
+        for the audio-only net).  Row b of the result equals forward on the utterance alone at its frames and is 0
+        after them.  The two-stream branch schedule is forward's.  The LSTM is causal and runs over all Tmax frames:
+        what it computes at a row's padding frames follows its valid ones and is multiplied by the zero spectrum."""
+        if self.training:
+            raise RuntimeError("AVNet.forward_ragged is an inference path: call .eval() first")
+        if torch.is_autocast_enabled():
+            raise RuntimeError("AVNet.forward_ragged runs in fp32: leave the autocast region")
+        spec = inp["noisy_audio_spec"]
+        Bn, T = spec.shape[0], spec.shape[2]
+        fl = K._lengths(frame_lengths, Bn, T, spec.device, "AVNet.forward_ragged (frame_lengths)")
+        vl = None
+        if not self.a_only:
+            lips = inp["lip_images"]
+            vl = K._lengths(vis_lengths, Bn, lips.shape[2], spec.device, "AVNet.forward_ragged (vis_lengths)")
+        side = None if self.a_only else _branch_stream(spec.device)
+        if side is not None:
+            main = torch.cuda.current_stream(spec.device)
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
+                vis = self.net_visualfeat.forward_ragged(lips, vl)
+            lips.record_stream(side)
+        audio = self.net_audiofeat.forward_ragged(spec, fl)
+        if self.a_only:
+            comb = audio
+        else:
+            if side is not None:
+                main.wait_stream(side)
+                vis.record_stream(main)
+            else:
+                vis = self.net_visualfeat.forward_ragged(lips, vl)
+            # model.py:124-126 per utterance: row floor(t Tv_b / T_b) of its own Tv_b lip frames, written straight into
+            # the left 512 columns of the concatenation (csrc/upsample.hip nearest_len_kernel)
+            comb = K.gather_nearest_len(vis.contiguous(), vl, fl, T, extra=audio.shape[-1])
+            comb[:, :, vis.shape[-1]:] = audio
+        mask = self.net_fusion(comb)
+        return spec * mask.unsqueeze(1)
+
+    @torch.no_grad()
+    def enhance_batch(self, items, batch_size=16, max_pad_ratio=1.25):
+        """enhance() for a list of utterances of different lengths (test.py:58-89 walks them one at a time): items are
+        (noisy_wave, lips) pairs or dicts with "noisy_audio" and "lip_images" -- a 1-D waveform and the (3, Tv, H, W)
+        lip frames (uint8 as stored, or float; all items alike; None / absent for the audio-only net).  They are cut
+        into batches by avse4.plan_ragged_batches (sorted by length, at most batch_size items, padded / useful samples
+        <= max_pad_ratio); each batch is one padded upload, the length-aware STFT, forward_ragged, the length-aware
+        iSTFT and one download.  Returns the estimates in the order of `items`, numpy float32 (T_b,)."""
+        from .avse4 import plan_ragged_batches
+        if self.training:
+            raise RuntimeError("AVNet.enhance_batch is an inference path: call .eval() first")
+        if torch.is_autocast_enabled():
+            raise RuntimeError("AVNet.enhance_batch runs in fp32: leave the autocast region")
+        if not items:
+            return []
+        import numpy as np
+        waves, clips = [], []
+        for it in items:
+            w, lp = (it["noisy_audio"], it.get("lip_images")) if isinstance(it, dict) else it
+            w = np.asarray(w.cpu() if torch.is_tensor(w) else w, dtype=np.float32)
+            if w.ndim != 1 or w.shape[0] < K.STFT_MIN_SAMPLES:
+                raise ValueError(f"enhance_batch: a 1-D waveform of at least {K.STFT_MIN_SAMPLES} samples is needed "
+                                 f"(reflect padding), got shape {w.shape}")
+            waves.append(w)
+            if not self.a_only:
+                if lp is None:
+                    raise ValueError("enhance_batch: lip frames are needed (the model is not audio-only)")
+                lp = np.asarray(lp.cpu() if torch.is_tensor(lp) else lp)
+                if lp.ndim != 4 or lp.shape[0] != 3 or lp.shape[1] < 1:
+                    raise ValueError(f"enhance_batch: lips must be (3, Tv >= 1, H, W), got {lp.shape}")
+                clips.append(lp if lp.dtype == np.uint8 else lp.astype(np.float32, copy=False))
+        if clips and any(c.shape[2:] != clips[0].shape[2:] or c.dtype != clips[0].dtype for c in clips):
+            raise ValueError("enhance_batch: all lip clips must share their frame size and dtype")
+        dev = next(self.parameters()).device
+        out = [None] * len(items)
+        for batch in plan_ragged_batches([w.shape[0] for w in waves], batch_size, max_pad_ratio):
+            tl = [waves[i].shape[0] for i in batch]
+            audio = np.zeros((len(batch), max(tl)), np.float32)
+            for b, i in enumerate(batch):
+                audio[b, :tl[b]] = waves[i]
+            wl = K.Lengths(tl, dev)
+            inp, vl = {}, None
+            if not self.a_only:
+                tv = [clips[i].shape[1] for i in batch]
+                video = np.zeros((len(batch), 3, max(tv)) + clips[0].shape[2:], clips[0].dtype)
+                for b, i in enumerate(batch):
+                    video[b, :, :tv[b]] = clips[i]
+                inp["lip_images"] = torch.from_numpy(video).to(dev)
+                vl = K.Lengths(tv, dev)
+            mag, spec = K.stft(torch.from_numpy(audio).to(dev), return_complex=True, lengths=wl)
+            inp["noisy_audio_spec"] = mag.unsqueeze(1)
+            fl = K.Lengths([K.stft_frames(t) for t in tl], dev)
+            pred = self.forward_ragged(inp, fl, vl)[:, 0]
+            est = K.istft(pred, spec, max(tl), lengths=wl).cpu().numpy()
+            for b, i in enumerate(batch):
+                out[i] = est[b, :tl[b]].copy()
+        return out
 
 
 def load_lightning_state_dict(model, ckpt_state_dict):

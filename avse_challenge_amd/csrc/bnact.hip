@@ -621,6 +621,82 @@ __global__ __launch_bounds__(THREADS) void bwd_kernel(PGeo p, const float* __res
 
 }  // namespace pool
 
+// ---- length-aware eval forward for zero-padded ragged batches (inference only): y = act(BN(x)) where the element's
+// time index t lies in the sample's valid window toff <= t < toff + len[b], exact +0 elsewhere (a select: NaN or Inf in
+// x's padding does not reach y or the max).  The valid elements go through apply_kernel's expressions, so they equal
+// the dense eval forward bit for bit.  Where (b, t) comes from:
+//   rows mode  row r of the (N, C S) matrix = ((b T + t) inner + i): channels-last (B, T, F, C) and (B, T, H, W, C)
+//              with S = 1, the time-major TCN rows (inner = 1) and frame-major (B T, C, H, W) (inner = 1, S = H W);
+//   cols mode  N = B and column j = (c, t, i) with S = T inner: contiguous (B, C, T, F) / (B, C, T, H, W).
+// toff > 0 is the TCN's: BatchNorm runs on the conv's unchomped (T + pad) output, the valid window is the part the
+// symmetric chomp keeps.  MODE 0 writes fp32 y and publishes max |y|; MODE 1 only publishes that max (over valid
+// elements: the split scale of MODE 2 must be known before its pass); MODE 2 writes the split layout of apply_kernel's
+// QOUT under *ymax.
+struct LenGeo {
+    int T, inner, toff, rows;
+};
+
+__device__ inline bool len_ok(const LenGeo& lg, const int32_t* __restrict__ lengths, int b, int t) {
+    const int n = min(max(lengths[b], 0), lg.T - lg.toff);
+    return t >= lg.toff && t - lg.toff < n;
+}
+
+template <int V, int ACT, int MODE>
+__global__ __launch_bounds__(THREADS) void apply_len_kernel(Geo g, LenGeo lg, const float* __restrict__ x,
+                                                            const int32_t* __restrict__ lengths,
+                                                            const float* __restrict__ stats,
+                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                            const float* __restrict__ alpha, int alpha_n,
+                                                            float* __restrict__ y, uint32_t* __restrict__ ymax) {
+    const int tx = threadIdx.x % g.TW, ty = threadIdx.x / g.TW;
+    const int64_t j0 = ((int64_t)blockIdx.x * g.TW + tx) * V;
+    float m = 0.f;
+    float sc = 1.f;
+    if constexpr (MODE == 2) sc = split_scale(*ymax);
+    if (j0 < g.CS) {
+        ColConst<V, ACT> cc;
+        cc.load(g, j0, stats, gamma, beta, alpha, alpha_n);
+        int tc[V];                                           // cols mode: the columns' time indices
+#pragma unroll
+        for (int k = 0; k < V; ++k) tc[k] = lg.rows ? 0 : (int)(((j0 + k) % g.S) / lg.inner);
+        for (int64_t r = (int64_t)blockIdx.y * g.RPI + ty; r < g.N; r += (int64_t)gridDim.y * g.RPI) {
+            const int64_t o = r * g.CS + j0;
+            bool ok[V];
+            bool any = false;
+            if (lg.rows) {
+                const int64_t q = r / lg.inner;
+                const int b = (int)(q / lg.T), t = (int)(q - (int64_t)b * lg.T);
+                any = len_ok(lg, lengths, b, t);
+#pragma unroll
+                for (int k = 0; k < V; ++k) ok[k] = any;
+            } else {
+#pragma unroll
+                for (int k = 0; k < V; ++k) {
+                    ok[k] = len_ok(lg, lengths, (int)r, tc[k]);
+                    any |= ok[k];
+                }
+            }
+            float v[V];
+#pragma unroll
+            for (int k = 0; k < V; ++k) v[k] = 0.f;
+            if (any) {                                       // a wholly padded vector is not loaded
+                vld<V>::ld(x + o, v);
+#pragma unroll
+                for (int k = 0; k < V; ++k) {
+                    const float z = act_fwd<ACT>(cc.preact(v[k], k), cc.al[k]);
+                    v[k] = ok[k] ? z : 0.f;
+                    m = fmaxf(m, fabsf(v[k]));
+                }
+            }
+            if constexpr (MODE == 0) vld<V>::st(y + o, v);
+            if constexpr (MODE == 2 && V == 4) q_store4(reinterpret_cast<uint16_t*>(y), r, g.CS, j0, v, sc);
+        }
+    }
+    if constexpr (MODE != 2) {
+        if (ymax) block_max_out(m, ymax);                    // workgroup-uniform condition
+    }
+}
+
 // ---- host side
 inline int pow2ceil(int64_t v) {
     int p = 1;
@@ -685,6 +761,21 @@ struct dispatch_q {
 };
 template <int V, int A, bool R> struct BwdPartK { static constexpr auto fn = bwd_partial_kernel<V, A, R>; };
 template <int V, int A, bool R> struct BwdApplyK { static constexpr auto fn = bwd_apply_kernel<V, A, R>; };
+
+template <int V, int MODE>
+inline void launch_apply_len(int act, dim3 grid, hipStream_t st, const Geo& g, const LenGeo& lg, const float* x,
+                             const int32_t* lengths, const float* stats, const float* gamma, const float* beta,
+                             const float* alpha, int alpha_n, float* y, uint32_t* y_max) {
+    if (act == ACT_NONE)
+        hipLaunchKernelGGL((apply_len_kernel<V, ACT_NONE, MODE>), grid, dim3(THREADS), 0, st, g, lg, x, lengths, stats,
+                           gamma, beta, alpha, alpha_n, y, y_max);
+    else if (act == ACT_RELU)
+        hipLaunchKernelGGL((apply_len_kernel<V, ACT_RELU, MODE>), grid, dim3(THREADS), 0, st, g, lg, x, lengths, stats,
+                           gamma, beta, alpha, alpha_n, y, y_max);
+    else
+        hipLaunchKernelGGL((apply_len_kernel<V, ACT_PRELU, MODE>), grid, dim3(THREADS), 0, st, g, lg, x, lengths, stats,
+                           gamma, beta, alpha, alpha_n, y, y_max);
+}
 
 }  // namespace bnact
 }  // namespace avse
@@ -769,6 +860,64 @@ int avse_bnact_fwd_q(int64_t N, int64_t C, int64_t S, const float* x, const floa
                      avse_stream_t stream) {
     return bnact_fwd_impl(N, C, S, x, nullptr, gamma, beta, act, alpha, alpha_n, 1, eps, momentum, running_mean,
                           running_var, stats, (float*)yq, workspace, y_bound, true, (hipStream_t)stream);
+}
+
+// the length-aware eval forward (apply_len_kernel): eval_stats_kernel (which resets *y_max), then for the split output
+// the max pass and the split pass, else the one fp32 pass
+static int bnact_fwd_len_impl(int64_t N, int64_t C, int64_t S, const float* x, const float* gamma, const float* beta,
+                              int32_t act, const float* alpha, int32_t alpha_n, int32_t training, float eps,
+                              const float* running_mean, const float* running_var, float* stats, float* y,
+                              uint32_t* y_max, const int32_t* lengths, int64_t B, int64_t T, int64_t inner, int64_t t_off,
+                              int32_t time_in_rows, bool qout, hipStream_t st) {
+    if (!x || !y || !stats || !lengths || !running_mean || !running_var || (act == ACT_PRELU && !alpha)) return AVSE_EINVAL;
+    if (training) return AVSE_EINVAL;                    // inference only: there is no length-aware statistics pass
+    if (qout && !y_max) return AVSE_EINVAL;
+    if (!shape_ok(N, C, S) || act < ACT_NONE || act > ACT_PRELU) return AVSE_ESHAPE;
+    if (act == ACT_PRELU && alpha_n != 1 && alpha_n != C) return AVSE_ESHAPE;
+    if (B <= 0 || T <= 0 || inner <= 0 || t_off < 0 || t_off >= T || B > 0x7FFFFFFF || T > 0x7FFFFFFF ||
+        inner > 0x7FFFFFFF)
+        return AVSE_ESHAPE;
+    if (time_in_rows ? (N / T / inner != B || B * T * inner != N) : (N != B || S / inner != T || T * inner != S))
+        return AVSE_ESHAPE;
+    const int V = ((C * S) % 4 == 0 && al16(x) && al16(y)) ? 4 : 1;
+    if (qout && (S != 1 || C % 64 || V != 4 || !time_in_rows)) return AVSE_ESHAPE;
+    const Geo g = make_geo(N, C, S, V);
+    const LenGeo lg{(int)T, (int)inner, (int)t_off, time_in_rows ? 1 : 0};
+    const dim3 grid(g.tiles, g.nrb);
+    hipLaunchKernelGGL(eval_stats_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, st, (int)C, running_mean,
+                       running_var, eps, stats, y_max);
+    AVSE_CHECK_LAUNCH();
+    const float* cs = stats;
+    if (qout) {
+        launch_apply_len<4, 1>(act, grid, st, g, lg, x, lengths, cs, gamma, beta, alpha, (int)alpha_n, y, y_max);
+        AVSE_CHECK_LAUNCH();
+        launch_apply_len<4, 2>(act, grid, st, g, lg, x, lengths, cs, gamma, beta, alpha, (int)alpha_n, y, y_max);
+    } else if (V == 4) {
+        launch_apply_len<4, 0>(act, grid, st, g, lg, x, lengths, cs, gamma, beta, alpha, (int)alpha_n, y, y_max);
+    } else {
+        launch_apply_len<1, 0>(act, grid, st, g, lg, x, lengths, cs, gamma, beta, alpha, (int)alpha_n, y, y_max);
+    }
+    AVSE_CHECK_LAUNCH();
+    return AVSE_OK;
+}
+
+int avse_bnact_fwd_len(int64_t N, int64_t C, int64_t S, const float* x, const float* gamma, const float* beta,
+                       int32_t act, const float* alpha, int32_t alpha_n, int32_t training, float eps,
+                       const float* running_mean, const float* running_var, float* stats, float* y, uint32_t* y_max,
+                       const int32_t* lengths, int64_t B, int64_t T, int64_t inner, int64_t t_off, int32_t time_in_rows,
+                       avse_stream_t stream) {
+    return bnact_fwd_len_impl(N, C, S, x, gamma, beta, act, alpha, alpha_n, training, eps, running_mean, running_var,
+                              stats, y, y_max, lengths, B, T, inner, t_off, time_in_rows, false, (hipStream_t)stream);
+}
+
+int avse_bnact_fwd_q_len(int64_t N, int64_t C, int64_t S, const float* x, const float* gamma, const float* beta,
+                         int32_t act, const float* alpha, int32_t alpha_n, int32_t training, float eps,
+                         const float* running_mean, const float* running_var, float* stats, void* yq, uint32_t* y_max,
+                         const int32_t* lengths, int64_t B, int64_t T, int64_t inner, int64_t t_off, int32_t time_in_rows,
+                         avse_stream_t stream) {
+    return bnact_fwd_len_impl(N, C, S, x, gamma, beta, act, alpha, alpha_n, training, eps, running_mean, running_var,
+                              stats, (float*)yq, y_max, lengths, B, T, inner, t_off, time_in_rows, true,
+                              (hipStream_t)stream);
 }
 
 static int bnact_bwd_impl(int64_t N, int64_t C, int64_t S, const float* x, const float* res, const float* dy,

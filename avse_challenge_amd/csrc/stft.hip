@@ -200,6 +200,146 @@ __global__ __launch_bounds__(256) void istft_ola_kernel(int batch, int fstride, 
     out[i] = y;
 }
 
+// ---- length-aware siblings for zero-padded ragged batches (inference): row b holds T_b = clamp(lengths[b], 0, T)
+// samples at row stride T and has F_b = 1 + T_b / HOP frames (0 when T_b <= NFFT / 2: the reflect pad is undefined).
+// A frame f < F_b is the dense kernel's frame of the row cropped to T_b (the reflection at the row's own end, the same
+// arithmetic per element); frames f >= F_b are written as 0 without a load, so what the row holds past T_b is never
+// read.
+__device__ inline int row_frames(int Tb) { return Tb > NFFT / 2 ? 1 + Tb / HOP : 0; }
+
+__global__ __launch_bounds__(THREADS) void stft_len_kernel(int batch, int T, int frames, const float* __restrict__ wave,
+                                                           const int32_t* __restrict__ lengths, float* __restrict__ mag,
+                                                           float* __restrict__ spec) {
+    __shared__ Tables tab;
+    __shared__ float2 bufA[WAVES][NC], bufB[WAVES][NC];
+    init_tables(tab);
+    __syncthreads();
+    const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int fid = blockIdx.x * WAVES + wid;
+    if (fid >= batch * frames) return;
+    const int b = fid / frames, f = fid % frames;
+    const int Tb = min(max(lengths[b], 0), T);
+    float* mrow = mag + (int64_t)fid * NB;
+    float* srow = spec ? spec + (int64_t)fid * NB * 2 : nullptr;
+    if (f >= row_frames(Tb)) {
+        for (int k = lane; k < NB; k += 64) {
+            mrow[k] = 0.f;
+            if (srow) *reinterpret_cast<float2*>(&srow[2 * k]) = make_float2(0.f, 0.f);
+        }
+        return;
+    }
+    const float* wr = wave + (int64_t)b * T;
+#pragma unroll
+    for (int e = 0; e < 8; e += 2) {
+        float xs[2];
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int n = 8 * lane + e + q;
+            int i = f * HOP + n - NFFT / 2;
+            i = i < 0 ? -i : i;
+            i = i >= Tb ? 2 * (Tb - 1) - i : i;           // in [0, Tb): f HOP <= Tb and Tb > NFFT / 2
+            xs[q] = wr[i] * tab.win[n];
+        }
+        bufA[wid][4 * lane + e / 2] = make_float2(xs[0], xs[1]);
+    }
+    __builtin_amdgcn_wave_barrier();
+    float2* Z = fft256(bufA[wid], bufB[wid], tab, lane);
+#pragma unroll
+    for (int q = 0; q < 5; ++q) {
+        const int k = lane + 64 * q;
+        if (k <= NC && (q < 4 || lane == 0)) {
+            const float2 zk = Z[k & 255];
+            const float2 zr = cconj(Z[(NC - k) & 255]);
+            const float2 E = make_float2(0.5f * (zk.x + zr.x), 0.5f * (zk.y + zr.y));
+            const float2 dd = csub(zk, zr);
+            const float2 O = make_float2(0.5f * dd.y, -0.5f * dd.x);
+            const float2 X = cadd(E, cmul(tab.tw512[k], O));
+            mrow[k] = sqrtf(X.x * X.x + X.y * X.y);
+            if (srow) *reinterpret_cast<float2*>(&srow[2 * k]) = X;
+        }
+    }
+}
+
+// istft_frames_kernel for the frames f < F_b only: the others are neither read nor written (the overlap-add below never
+// reads them)
+__global__ __launch_bounds__(THREADS) void istft_frames_len_kernel(int batch, int frames, int length,
+                                                                   const int32_t* __restrict__ lengths,
+                                                                   const float* __restrict__ mag,
+                                                                   const float* __restrict__ phase,
+                                                                   float* __restrict__ out) {
+    __shared__ Tables tab;
+    __shared__ float2 bufA[WAVES][NC], bufB[WAVES][NC];
+    __shared__ float2 X[WAVES][NB];
+    init_tables(tab);
+    __syncthreads();
+    const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int fid = blockIdx.x * WAVES + wid;
+    if (fid >= batch * frames) return;
+    const int b = fid / frames, f = fid % frames;
+    if (f >= row_frames(min(max(lengths[b], 0), length))) return;
+    const float* mrow = mag + (int64_t)fid * NB;
+    const float* prow = phase + (int64_t)fid * NB * 2;
+    for (int k = lane; k < NB; k += 64) {
+        const float2 p = *reinterpret_cast<const float2*>(&prow[2 * k]);
+        const float r = sqrtf(p.x * p.x + p.y * p.y);
+        const float2 u = r > 0.f ? make_float2(p.x / r, p.y / r) : make_float2(1.f, 0.f);
+        float2 v = make_float2(mrow[k] * u.x, mrow[k] * u.y);
+        if (k == 0 || k == NC) v.y = 0.f;
+        X[wid][k] = v;
+    }
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int k = lane + 64 * q;
+        const float2 xk = X[wid][k];
+        const float2 xr = cconj(X[wid][NC - k]);
+        const float2 E = make_float2(0.5f * (xk.x + xr.x), 0.5f * (xk.y + xr.y));
+        const float2 Od = make_float2(0.5f * (xk.x - xr.x), 0.5f * (xk.y - xr.y));
+        const float2 O = cmul(Od, cconj(tab.tw512[k]));
+        const float2 Z = make_float2(E.x - O.y, E.y + O.x);
+        bufA[wid][k] = cconj(Z);
+    }
+    __builtin_amdgcn_wave_barrier();
+    float2* z = fft256(bufA[wid], bufB[wid], tab, lane);
+    float* orow = out + (int64_t)fid * NFFT;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int m = lane + 64 * q;
+        const float2 v = z[m];
+        const float xe = v.x * (1.f / 256.f), xo = -v.y * (1.f / 256.f);
+        *reinterpret_cast<float2*>(&orow[2 * m]) = make_float2(xe * tab.win[2 * m], xo * tab.win[2 * m + 1]);
+    }
+}
+
+// istft_ola_kernel with the row's own frame count (at most the fstride frames the buffers hold) and length: 0 from
+// T_b on
+__global__ __launch_bounds__(256) void istft_ola_len_kernel(int batch, int fstride, int length,
+                                                            const int32_t* __restrict__ lengths,
+                                                            const float* __restrict__ fb, float* __restrict__ out) {
+    const int64_t total = (int64_t)batch * length;
+    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int b = (int)(i / length), t = (int)(i % length);
+    const int Tb = min(max(lengths[b], 0), length);
+    const int frames = min(row_frames(Tb), fstride);
+    const int p = t + NFFT / 2;
+    const int ylen = NFFT + HOP * (frames - 1);
+    float y = 0.f, wss = 0.f;
+    if (t < Tb && frames > 0 && p < ylen) {
+        int f0 = (p - NFFT + HOP) / HOP;
+        if (p < NFFT - 1) f0 = 0;
+        const int f1 = min(frames - 1, p / HOP);
+        for (int f = f0; f <= f1; ++f) {
+            const int n = p - f * HOP;
+            y += fb[((int64_t)b * fstride + f) * NFFT + n];
+            const float w = 0.5f - 0.5f * cospif((float)n / 256.f);
+            wss += w * w;
+        }
+        if (wss > 1.17549435e-38f) y /= wss;
+    }
+    out[i] = y;
+}
+
 }  // namespace stft
 }  // namespace avse
 
@@ -237,6 +377,36 @@ int avse_istft(int64_t batch, int64_t frames, int64_t length, const float* mag, 
     const int64_t tot = batch * length;
     hipLaunchKernelGGL(istft_ola_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, (int)batch,
                        (int)frames, (int)used, (int)length, frames_buf, wave_out);
+    AVSE_CHECK_LAUNCH();
+    return AVSE_OK;
+}
+
+int avse_stft_fwd_len(int64_t batch, int64_t T, const float* wave, const int32_t* lengths, float* mag, float* spec,
+                      avse_stream_t stream) {
+    if (!wave || !lengths || !mag) return AVSE_EINVAL;
+    if (batch <= 0 || T <= NFFT / 2 || batch * T > (1LL << 31) - 1) return AVSE_ESHAPE;
+    const int frames = (int)avse_stft_frames(T);
+    const int64_t nf = batch * frames;
+    hipLaunchKernelGGL(stft_len_kernel, dim3((unsigned)((nf + WAVES - 1) / WAVES)), dim3(THREADS), 0,
+                       (hipStream_t)stream, (int)batch, (int)T, frames, wave, lengths, mag, spec);
+    AVSE_CHECK_LAUNCH();
+    return AVSE_OK;
+}
+
+int avse_istft_len(int64_t batch, int64_t frames, int64_t length, const float* mag, const float* phase,
+                   const int32_t* lengths, float* frames_buf, float* wave_out, avse_stream_t stream) {
+    if (!mag || !phase || !lengths || !frames_buf || !wave_out) return AVSE_EINVAL;
+    if (batch <= 0 || frames <= 0 || length <= 0 || batch * length > (1LL << 31) - 1 ||
+        batch * frames > (1LL << 31) / NFFT)
+        return AVSE_ESHAPE;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t nf = batch * frames;
+    hipLaunchKernelGGL(istft_frames_len_kernel, dim3((unsigned)((nf + WAVES - 1) / WAVES)), dim3(THREADS), 0, st,
+                       (int)batch, (int)frames, (int)length, lengths, mag, phase, frames_buf);
+    AVSE_CHECK_LAUNCH();
+    const int64_t tot = batch * length;
+    hipLaunchKernelGGL(istft_ola_len_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, (int)batch,
+                       (int)frames, (int)length, lengths, frames_buf, wave_out);
     AVSE_CHECK_LAUNCH();
     return AVSE_OK;
 }

@@ -38,6 +38,38 @@ __global__ __launch_bounds__(THREADS) void linear_len_kernel(int C, int n_in_max
     }
 }
 
+// Per-utterance nearest-neighbour gather of the avse1 lip features onto the audio frames (time-major rows): replaces,
+// per sample, F.interpolate(vis, size=(T_b, C), mode="nearest") of baseline/avse1/model.py:124-126, i.e.
+//   out[b, t, :C] = vis[b, (t n_in) / n_out, :C]  (integer division: torch.div(..., rounding_mode="floor"))  for t < n_out,
+// 0 for n_out <= t < T, with n_in = vlen[b], n_out = tlen[b].  out rows carry a row stride >= C: the left C columns of
+// the cat((vis, audio), -1) tensor the LSTM's input GEMM reads.  One workgroup per GROWS output rows, a wave per row.
+constexpr int GROWS = THREADS / 64;
+
+template <int V>
+__global__ __launch_bounds__(THREADS) void nearest_len_kernel(int C, int n_in_max, int T, const float* __restrict__ v,
+                                                              int64_t v_bs, int64_t v_ts,
+                                                              const int32_t* __restrict__ vlen,
+                                                              const int32_t* __restrict__ tlen, float* __restrict__ out,
+                                                              int64_t o_bs, int64_t o_ts, int64_t rows) {
+    const int64_t row = (int64_t)blockIdx.x * GROWS + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int lane = threadIdx.x & 63;
+    const int b = (int)(row / T), t = (int)(row - (int64_t)b * T);
+    const int n_in = min(max(vlen[b], 0), n_in_max), n_out = min(max(tlen[b], 0), T);
+    float* orow = out + b * o_bs + t * o_ts;
+    const bool ok = t < n_out && n_in > 0;
+    const int src = ok ? (int)(((int64_t)t * n_in) / n_out) : 0;          // < n_in since t < n_out
+    const float* vr = v + b * v_bs + src * v_ts;
+    for (int c = lane * V; c < C; c += 64 * V) {
+        if constexpr (V == 4) {
+            *reinterpret_cast<float4*>(orow + c) =
+                ok ? *reinterpret_cast<const float4*>(vr + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+        } else {
+            orow[c] = ok ? vr[c] : 0.f;
+        }
+    }
+}
+
 }  // namespace ups
 }  // namespace avse
 
@@ -56,6 +88,29 @@ int avse_upsample_linear_len(int64_t B, int64_t C, int64_t n_in_max, int64_t K, 
     if (v_cs < n_in_max || v_bs < C * v_cs || out_cs < K || out_bs < C * out_cs) return AVSE_ESHAPE;
     hipLaunchKernelGGL(linear_len_kernel, dim3((unsigned)(B * C)), dim3(THREADS), 0, (hipStream_t)stream, (int)C,
                        (int)n_in_max, (int)K, (int)up, v, v_bs, v_cs, vlen, klen, out, out_bs, out_cs);
+    AVSE_CHECK_LAUNCH();
+    return AVSE_OK;
+}
+
+int avse_gather_nearest_len(int64_t B, int64_t C, int64_t n_in_max, int64_t T, const float* v, int64_t v_bs, int64_t v_ts,
+                            const int32_t* vlen, const int32_t* tlen, float* out, int64_t out_bs, int64_t out_ts,
+                            avse_stream_t stream) {
+    if (!v || !vlen || !tlen || !out) return AVSE_EINVAL;
+    if (B <= 0 || C <= 0 || n_in_max <= 0 || T <= 0 || T > (1LL << 29) || n_in_max > (1LL << 29) || C > (1LL << 29) ||
+        B * T > (1LL << 31) - 1)
+        return AVSE_ESHAPE;
+    // rows must not overlap: a row's C elements inside its time stride, a sample's rows inside its batch stride
+    if (v_ts < C || v_bs < n_in_max * v_ts || out_ts < C || out_bs < T * out_ts) return AVSE_ESHAPE;
+    const int64_t rows = B * T;
+    const dim3 grid((unsigned)((rows + GROWS - 1) / GROWS));
+    const bool vec = C % 4 == 0 && v_bs % 4 == 0 && v_ts % 4 == 0 && out_bs % 4 == 0 && out_ts % 4 == 0 &&
+                     ((uintptr_t)v & 15) == 0 && ((uintptr_t)out & 15) == 0;
+    if (vec)
+        hipLaunchKernelGGL(nearest_len_kernel<4>, grid, dim3(THREADS), 0, (hipStream_t)stream, (int)C, (int)n_in_max,
+                           (int)T, v, v_bs, v_ts, vlen, tlen, out, out_bs, out_ts, rows);
+    else
+        hipLaunchKernelGGL(nearest_len_kernel<1>, grid, dim3(THREADS), 0, (hipStream_t)stream, (int)C, (int)n_in_max,
+                           (int)T, v, v_bs, v_ts, vlen, tlen, out, out_bs, out_ts, rows);
     AVSE_CHECK_LAUNCH();
     return AVSE_OK;
 }

@@ -543,30 +543,63 @@ def stft_frames(T):
     return int(_lib.lib().avse_stft_frames(T))
 
 
-def stft(wave, return_complex=False):
-    """wave (B, T) fp32 -> |STFT|.T (B, frames, 257) [and complex (B, frames, 257)]; librosa 0.8.1 semantics."""
+STFT_MIN_SAMPLES = 257          # reflect padding of n_fft / 2 = 256 samples needs one more
+
+
+def _wave_lengths(lengths, batch, extent, device, what):
+    """Lengths of waveform rows for the STFT kernels: [257, extent] each (the reflect pad is undefined below)."""
+    lengths = _lengths(lengths, batch, extent, device, what)
+    if min(lengths.host) < STFT_MIN_SAMPLES:
+        raise ValueError(f"{what}: a row of {min(lengths.host)} samples; reflect padding needs at least "
+                         f"{STFT_MIN_SAMPLES}")
+    return lengths
+
+
+def stft(wave, return_complex=False, lengths=None):
+    """wave (B, T) fp32 -> |STFT|.T (B, frames, 257) [and complex (B, frames, 257)]; librosa 0.8.1 semantics.
+    lengths (a sequence or a Lengths, 257 <= lengths[b] <= T): row b is the zero-padded utterance wave[b, :lengths[b]];
+    its 1 + lengths[b] // 128 frames are those of stft(wave[b:b+1, :lengths[b]]) bit for bit, the rest 0, and what the
+    row holds past lengths[b] is not read (avse_stft_fwd_len)."""
     _need_gpu(wave)
     wave = wave.float().contiguous()
     Bn, T = wave.shape
+    if lengths is not None:
+        lengths = _wave_lengths(lengths, Bn, T, wave.device, "stft")
     F = stft_frames(T)
     mag = torch.empty((Bn, F, 257), device=wave.device, dtype=torch.float32)
     spec = torch.empty((Bn, F, 257, 2), device=wave.device, dtype=torch.float32) if return_complex else None
-    check(_lib.lib().avse_stft_fwd(Bn, T, ptr(wave), ptr(mag), ptr(spec), stream_ptr(wave.device)), "avse_stft_fwd")
+    if lengths is not None:
+        check(_lib.lib().avse_stft_fwd_len(Bn, T, ptr(wave), ptr(lengths.dev), ptr(mag), ptr(spec),
+                                           stream_ptr(wave.device)), "avse_stft_fwd_len")
+    else:
+        check(_lib.lib().avse_stft_fwd(Bn, T, ptr(wave), ptr(mag), ptr(spec), stream_ptr(wave.device)), "avse_stft_fwd")
     if return_complex:
         return mag, torch.view_as_complex(spec)
     return mag
 
 
-def istft(mag, phase_spec, length):
-    """mag (B, frames, 257) and the complex spectrum whose angle is used (B, frames, 257) -> (B, length)."""
+def istft(mag, phase_spec, length, lengths=None):
+    """mag (B, frames, 257) and the complex spectrum whose angle is used (B, frames, 257) -> (B, length).
+    lengths (257 <= lengths[b] <= length, 1 + lengths[b] // 128 <= frames): row b is istft(mag[b:b+1, :F_b],
+    phase_spec[b:b+1, :F_b], lengths[b]) bit for bit with F_b = 1 + lengths[b] // 128, and 0 from lengths[b] on; frames
+    past F_b are not read (avse_istft_len)."""
     _need_gpu(mag, phase_spec)
     mag = mag.float().contiguous()
     ps = torch.view_as_real(phase_spec.to(torch.complex64)).contiguous()
     Bn, F, nb = mag.shape
     if nb != 257 or tuple(ps.shape[:3]) != (Bn, F, 257):
         raise RuntimeError("istft expects (B, frames, 257) magnitude and matching complex phase spectrum")
+    if lengths is not None:
+        lengths = _wave_lengths(lengths, Bn, length, mag.device, "istft")
+        if stft_frames(max(lengths.host)) > F:
+            raise ValueError(f"istft: a row of {max(lengths.host)} samples has {stft_frames(max(lengths.host))} frames, "
+                             f"the spectrum holds {F}")
     fbuf = torch.empty((Bn, F, 512), device=mag.device, dtype=torch.float32)
     out = torch.empty((Bn, length), device=mag.device, dtype=torch.float32)
+    if lengths is not None:
+        check(_lib.lib().avse_istft_len(Bn, F, length, ptr(mag), ptr(ps), ptr(lengths.dev), ptr(fbuf), ptr(out),
+                                        stream_ptr(mag.device)), "avse_istft_len")
+        return out
     check(_lib.lib().avse_istft(Bn, F, length, ptr(mag), ptr(ps), ptr(fbuf), ptr(out), stream_ptr(mag.device)),
           "avse_istft")
     return out
@@ -1238,17 +1271,61 @@ def _q_ok(x, res):
             and not x.is_contiguous() and x.data_ptr() % 16 == 0)
 
 
+def _bn_time_geo(x, N, S, frames):
+    """Where the time index of an element of x lies in the (N, C, S) view the bnact kernels read: (B, T, inner,
+    time_in_rows) of avse_bnact_fwd_len.  frames=None: time is axis 2 of (B, C, T, ...), contiguous (a column index) or
+    channels-last (a row index; the TCN's (B, C, T, 1) view of time-major rows included).  frames=T: x is
+    (B T, C, H, W), frame-major rows."""
+    if frames is not None:
+        if x.dim() != 4 or frames < 1 or x.shape[0] % frames:
+            raise ValueError(f"bnact_fwd: frames={frames} does not divide the {x.shape[0]} frames of a 4-D tensor")
+        # contiguous frames: a row per frame (S = H W); channels-last frames: a row per pixel (S = 1), H W rows per frame
+        return x.shape[0] // frames, frames, (1 if S > 1 else x.shape[2] * x.shape[3]), 1
+    if x.dim() < 3:
+        raise ValueError("bnact_fwd: lengths need a (B, C, T, ...) tensor")
+    B, T = x.shape[0], x.shape[2]
+    inner = x.numel() // max(1, B * x.shape[1] * T)
+    return B, T, inner, (0 if x.is_contiguous() else 1)
+
+
 def bnact_fwd(x, gamma, beta, running_mean, running_var, training, momentum, eps, act=ACT_NONE, alpha=None, res=None,
-              q_out=False):
+              q_out=False, lengths=None, frames=None, t_off=0):
     """act(BatchNorm(x) [+ res]); returns (y, stats (C, 4) = mean hi, mean lo, rstd, bound of max |x - mean|).  y keeps
     x's format.  q_out (training, channels-last, C % 64 == 0, no residual; otherwise ignored): y is a split-output
-    tensor (SPLITQ_ATTR)."""
+    tensor (SPLITQ_ATTR).
+    lengths (a sequence or a Lengths; eval mode, no residual): sample b's valid time steps are t_off <= t < t_off +
+    lengths[b] of the time axis (axis 2; with frames=T, x is (B T, C, H, W) and the time index is its row's frame); y is
+    exact 0 elsewhere, whatever x holds there, and the max y carries covers the valid part (avse_bnact_fwd_len).  q_out
+    then applies in eval mode (avse_bnact_fwd_q_len: the split under the exact valid max)."""
     _need_gpu(x)
     if x.dtype != torch.float32:
         raise RuntimeError("bnact kernels are fp32")
     if _bn_view(x) is None:
         x = x.contiguous()
     N, C, S = _bn_view(x)
+    if lengths is not None:
+        if training or res is not None:
+            raise RuntimeError("bnact_fwd: lengths are for the eval forward without a residual")
+        if running_mean is None or running_var is None:
+            raise RuntimeError("bnact_fwd: lengths need running statistics")
+        Bn, T, inner, in_rows = _bn_time_geo(x, N, S, frames)
+        if not 0 <= t_off < T:
+            raise ValueError(f"bnact_fwd: t_off {t_off} outside the {T} time steps")
+        lengths = _lengths(lengths, Bn, T - t_off, x.device, "bnact_fwd")
+        y = torch.empty_like(x)
+        stats = torch.empty((C, 4), device=x.device, dtype=torch.float32)
+        a = alpha.float().contiguous() if alpha is not None else None
+        ymax = torch.empty(1, device=x.device, dtype=torch.int32)
+        q = bool(q_out) and in_rows == 1 and frames is None and _q_ok(x, None)
+        fn, name = (_lib.lib().avse_bnact_fwd_q_len, "avse_bnact_fwd_q_len") if q else \
+            (_lib.lib().avse_bnact_fwd_len, "avse_bnact_fwd_len")
+        check(fn(N, C, S, ptr(x), _opt(gamma), _opt(beta), int(act), _opt(a), a.numel() if a is not None else 0, 0,
+                 float(eps), ptr(running_mean), ptr(running_var), ptr(stats), ptr(y), ptr(ymax), ptr(lengths.dev),
+                 Bn, T, inner, int(t_off), in_rows, stream_ptr(x.device)), name)
+        _set_absmax(y, ymax)
+        if q:
+            setattr(y, SPLITQ_ATTR, True)
+        return y, stats
     if res is not None:
         res = _same_layout(res.float(), x)
     y = torch.empty_like(x)
@@ -1456,6 +1533,30 @@ def upsample_linear_len(v, vis_lengths, lengths, up, out):
     check(_lib.lib().avse_upsample_linear_len(Bn, C, Tv, Kn, int(up), ptr(v), v.stride(0), v.stride(1), ptr(vl.dev),
                                               ptr(kl.dev), ptr(out), out.stride(0), out.stride(1),
                                               stream_ptr(v.device)), "avse_upsample_linear_len")
+    return out
+
+
+def gather_nearest_len(v, vis_lengths, lengths, T, extra=0, out=None):
+    """The avse1 lip-to-audio gather for a ragged batch: out[b, t, :C] = v[b, (t * vis_lengths[b]) // lengths[b]] for
+    t < lengths[b] and 0 for lengths[b] <= t < T -- per row the index torch.div(arange(T_b) * Tv_b, T_b,
+    rounding_mode="floor") of the dense forward (avse_gather_nearest_len).  v (B, Tv, C) fp32 with unit stride along C.
+    Returns out (B, T, C + extra), allocated here unless given, of which only the left C columns are written: the
+    cat((vis, audio), -1) tensor whose right `extra` columns the caller fills."""
+    if v.dim() != 3:
+        raise ValueError(f"gather_nearest_len: v {tuple(v.shape)} must be (B, Tv, C)")
+    Bn, Tv, C = v.shape
+    vl = _lengths(vis_lengths, Bn, Tv, v.device, "gather_nearest_len (vis_lengths)")
+    tl = _lengths(lengths, Bn, T, v.device, "gather_nearest_len (lengths)")
+    _need_gpu(v)
+    if out is None:
+        out = torch.empty((Bn, T, C + extra), device=v.device, dtype=torch.float32)
+    if tuple(out.shape[:2]) != (Bn, T) or out.shape[2] < C:
+        raise ValueError(f"gather_nearest_len: out {tuple(out.shape)} must be ({Bn}, {T}, >= {C})")
+    if v.dtype != torch.float32 or out.dtype != torch.float32 or v.stride(2) != 1 or out.stride(2) != 1:
+        raise ValueError("gather_nearest_len: fp32 tensors with unit stride along the channels")
+    check(_lib.lib().avse_gather_nearest_len(Bn, C, Tv, T, ptr(v), v.stride(0), v.stride(1), ptr(vl.dev), ptr(tl.dev),
+                                             ptr(out), out.stride(0), out.stride(1), stream_ptr(v.device)),
+          "avse_gather_nearest_len")
     return out
 
 

@@ -122,7 +122,7 @@ class _BNActFn(torch.autograd.Function):
                 dalpha if ctx.needs_input_grad[3] else None, dres, None, None, None, None, None, None, None, None)
 
 
-def bn_act(x, bn, act=None, res=None, folded_bias=None, q_fwd=False, q_bwd=False):
+def bn_act(x, bn, act=None, res=None, folded_bias=None, q_fwd=False, q_bwd=False, lengths=None, frames=None, t_off=0):
     """act(bn(x) [+ res]) for an nn.BatchNorm{1,2,3}d `bn` (its parameters, buffers, momentum and eps; running
     statistics and num_batches_tracked updated in train mode as torch does).  act: None, "relu" or a PReLU module.
     x: fp32 contiguous or channels-last; the output keeps x's memory format.
@@ -134,7 +134,21 @@ def bn_act(x, bn, act=None, res=None, folded_bias=None, q_fwd=False, q_bwd=False
     the backward here then skips its reduction pass over x and dy.
     folded_bias (training mode only): x is a convolution output whose per-channel bias was left out; the result is
     act(bn(x + bias)) — equal to act(bn(x)), the batch statistics shift with the bias — and the running mean takes
-    the bias in (momentum * bias)."""
+    the bias in (momentum * bias).
+    lengths (a sequence or a kernels.Lengths; ragged inference: eval-mode bn with running statistics, no residual, no
+    gradient recorded): the result is exact 0 outside each sample's valid time steps [t_off, t_off + lengths[b]) of
+    axis 2 (or, with frames=T, of the frame index of a (B T, C, H, W) x), whatever x holds there, and q_fwd takes
+    effect in eval mode (kernels.bnact_fwd with lengths)."""
+    if lengths is not None:
+        if bn.training or not bn.track_running_stats or res is not None or folded_bias is not None:
+            raise RuntimeError("bn_act: lengths need an eval-mode BatchNorm with running statistics, no residual")
+        if torch.is_grad_enabled() and (x.requires_grad or (bn.weight is not None and bn.weight.requires_grad)):
+            raise RuntimeError("bn_act: the length-aware forward has no backward (run it under torch.no_grad())")
+        if not x.is_cuda:
+            raise RuntimeError("bn_act runs on the GPU kernels only")
+        _, code, alpha, rm, rv, _ = _bn_module_args(bn, act)
+        return K.bnact_fwd(x.float(), bn.weight, bn.bias, rm, rv, False, 0.0, bn.eps, code, alpha, q_out=bool(q_fwd),
+                           lengths=lengths, frames=frames, t_off=t_off)[0]
     if folded_bias is not None:
         if not (bn.training and bn.track_running_stats) or res is not None or bn.momentum is None:
             raise RuntimeError("bn_act: folded_bias needs a training-mode BatchNorm with running stats and a momentum "

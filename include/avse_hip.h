@@ -532,6 +532,51 @@ int avse_upsample_linear_len(int64_t B, int64_t C, int64_t n_in_max, int64_t K, 
                              int64_t v_cs, const int32_t* vlen, const int32_t* klen, float* out, int64_t out_bs,
                              int64_t out_cs, avse_stream_t stream);
 
+/* ---------------------------------------------------------------- ragged inference batches (avse1) ----
+ * The avse1 front-end, BatchNorm passes and lip-to-audio gather for a zero-padded batch of utterances of different
+ * lengths (baseline/avse1/test.py:58-89 walks the set one scene at a time).  lengths: device int32, one per sample,
+ * clamped in the kernels so that no value moves an access out of a row.  Inference only: no backward exists.
+ *
+ * avse_stft_fwd_len: avse_stft_fwd on rows of T_b = lengths[b] samples at row stride T.  Row b has F_b = 1 + T_b / 128
+ * frames (0 when T_b <= 256), reflect-padded at its own end: frames f < F_b equal avse_stft_fwd on the row cropped to
+ * T_b bit for bit, mag / spec are +0 for F_b <= f < 1 + T / 128, and wave[b, T_b:] is never read.
+ * avse_istft_len: avse_istft with the row's own F_b (at most `frames`) and T_b = lengths[b] <= length: the overlap-add
+ * and the window-sum normalisation of the row cropped to (F_b, T_b), bit for bit, +0 from T_b to length; frames
+ * f >= F_b of mag / phase_spec are never read. */
+int avse_stft_fwd_len(int64_t batch, int64_t T, const float* wave, const int32_t* lengths, float* mag,
+                      float* spec_or_null, avse_stream_t stream);
+int avse_istft_len(int64_t batch, int64_t frames, int64_t length, const float* mag, const float* phase_spec,
+                   const int32_t* lengths, float* frames_buf, float* wave_out, avse_stream_t stream);
+/* Eval-mode avse_bnact_fwd (no residual) whose output is exact +0 outside each sample's valid window of the time axis:
+ * y = act(BN(x)) where t_off <= t < t_off + lengths[b] (lengths clamped into [0, T - t_off]), +0 elsewhere by a select
+ * (NaN / Inf in x there reach neither y nor y_max).  The valid elements equal avse_bnact_fwd's bit for bit; y_max (may be
+ * null) is max |y| over them.  (b, t) of an element of the (N, C, S) view:
+ *   time_in_rows != 0: N = B T inner, row r = (b T + t) inner + i -- channels-last (B, T, F, C) and (B, T, H, W, C)
+ *                      (S = 1, inner = F or H W), time-major (B T, C) rows (inner = 1), frames (B T, C, H, W);
+ *   time_in_rows == 0: N = B, S = T inner, column (c, t, i) -- contiguous (B, C, T, F) and (B, C, T, H, W).
+ * t_off > 0 serves a BatchNorm over a padded convolution output of which a later chomp keeps [t_off, t_off + T').
+ * training != 0 is refused (AVSE_EINVAL): there is no length-aware statistics pass.  stats as avse_bnact_fwd's (eval).
+ * avse_bnact_fwd_q_len writes the split layout of avse_bnact_fwd_q (channels-last: S = 1, C % 64 == 0, time_in_rows,
+ * 16-B aligned) under the exact max over the valid elements, found by a pass of its own and left in *y_max: the bytes
+ * avse_split16_known makes of avse_bnact_fwd_len's output under that word. */
+int avse_bnact_fwd_len(int64_t N, int64_t C, int64_t S, const float* x, const float* gamma, const float* beta,
+                       int32_t act, const float* alpha, int32_t alpha_n, int32_t training, float eps,
+                       const float* running_mean, const float* running_var, float* stats, float* y, uint32_t* y_max,
+                       const int32_t* lengths, int64_t B, int64_t T, int64_t inner, int64_t t_off, int32_t time_in_rows,
+                       avse_stream_t stream);
+int avse_bnact_fwd_q_len(int64_t N, int64_t C, int64_t S, const float* x, const float* gamma, const float* beta,
+                         int32_t act, const float* alpha, int32_t alpha_n, int32_t training, float eps,
+                         const float* running_mean, const float* running_var, float* stats, void* yq, uint32_t* y_max,
+                         const int32_t* lengths, int64_t B, int64_t T, int64_t inner, int64_t t_off, int32_t time_in_rows,
+                         avse_stream_t stream);
+/* Nearest-neighbour gather of the lip features onto the audio frames (baseline/avse1/model.py:124-126,
+ * F.interpolate(mode="nearest") over time): out[b, t, :C] = v[b, (t vlen[b]) / tlen[b], :C] (integer division) for
+ * t < tlen[b], +0 for tlen[b] <= t < T.  v (B, n_in_max, C), out (B, T, >= C): element strides of the batch and time
+ * axes (unit stride along C), so out may be the left C columns of a wider tensor. */
+int avse_gather_nearest_len(int64_t B, int64_t C, int64_t n_in_max, int64_t T, const float* v, int64_t v_bs, int64_t v_ts,
+                            const int32_t* vlen, const int32_t* tlen, float* out, int64_t out_bs, int64_t out_ts,
+                            avse_stream_t stream);
+
 /* ---------------------------------------------------------------- LSTM recurrence ----------
  * Replaces the per-step cuDNN/MIOpen LSTM behind nn.LSTM at baseline/avse1/model.py:88 (FusionNet:
  * LSTM(1540 -> 257), batch_first) and baseline/avse2/model.py:101-102 (DPRNN, bidirectional: one call per
