@@ -222,6 +222,9 @@ SIGNATURES = {
     "avse_bnact_fwd_q_len": (c_i32, [c_i64] * 3 + [c_vp] * 3 + [c_i32, c_vp, c_i32, c_i32, c_f32] + [c_vp] * 6
                              + [c_i64] * 4 + [c_i32, c_vp]),
     "avse_gather_nearest_len": (c_i32, [c_i64] * 4 + [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp]),
+    # the DPMamba ragged path: channels-last GroupNorm(1, N) over each row's valid lines
+    "avse_gln_cl_workspace_bytes": (c_i64, [c_i64] * 3),
+    "avse_gln_cl_fwd_len": (c_i32, [c_i64] * 4 + [c_vp, c_vp, c_i32, c_vp, c_vp, c_f32, c_vp, c_i32] + [c_vp] * 4),
     "avse_lstm_padded_hidden": (c_i64, [c_i64]),
     "avse_lstm_group_size": (c_i64, [c_i64, c_i64]),
     "avse_lstm_group_workspace_bytes": (c_i64, [c_i64, c_i64]),

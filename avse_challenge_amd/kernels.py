@@ -1560,6 +1560,46 @@ def gather_nearest_len(v, vis_lengths, lengths, T, extra=0, out=None):
     return out
 
 
+# ------------------------------------------------------------------------ channels-last GroupNorm(1, N) (DPMamba)
+
+def gln_cl_fwd(x, gamma, beta, eps, lengths, len_axis, res=None, transpose_out=False):
+    """GroupNorm(1, N) of the rows of a zero-padded ragged batch stored channels-last (avse_gln_cl_fwd_len, inference
+    only).  x (B, R, C, N) fp32; row b is valid for r < lengths[b] (len_axis 0) or c < lengths[b] (len_axis 1), is
+    normalised over its valid elements alone (biased variance, eps inside the rsqrt) and comes out +0 elsewhere; what
+    x and res hold there is not used.  res (the output's shape) is added after the affine.  transpose_out: y is written
+    as (B, C, R, N).  lengths: an int32 device tensor of B entries (clamped into the axis by the kernel), or a sequence
+    or Lengths of values in [0, extent].  Returns (y, stats (B, 2) = mean, rstd; (0, 0) for an empty row)."""
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise ValueError(f"gln_cl_fwd: x must be fp32 (B, R, C, N), got {x.dtype} {tuple(x.shape)}")
+    if len_axis not in (0, 1):
+        raise ValueError(f"gln_cl_fwd: len_axis must be 0 or 1, got {len_axis}")
+    Bn, R, C, N = x.shape
+    if torch.is_tensor(lengths) and lengths.is_cuda:
+        if lengths.dtype != torch.int32 or tuple(lengths.shape) != (Bn,) or lengths.device != x.device:
+            raise ValueError(f"gln_cl_fwd: lengths must be {Bn} int32 entries on {x.device}")
+        ldev = lengths.contiguous()
+    else:
+        ln = lengths if isinstance(lengths, Lengths) else Lengths(lengths, x.device)
+        extent = (R, C)[len_axis]
+        if len(ln.host) != Bn or min(ln.host) < 0 or max(ln.host) > extent or ln.dev.device != x.device:
+            raise ValueError(f"gln_cl_fwd: {Bn} lengths in [0, {extent}] on {x.device}, got {ln.host}")
+        ldev = ln.dev
+    _need_gpu(x, gamma, beta, res)
+    x = x.contiguous()
+    y = torch.empty((Bn, C, R, N) if transpose_out else (Bn, R, C, N), device=x.device, dtype=torch.float32)
+    if res is not None:
+        if res.shape != y.shape or res.dtype != torch.float32:
+            raise ValueError(f"gln_cl_fwd: res must be fp32 {tuple(y.shape)}, got {res.dtype} {tuple(res.shape)}")
+        res = res.contiguous()
+    stats = torch.empty((Bn, 2), device=x.device, dtype=torch.float32)
+    L = _lib.lib()
+    ws = torch.empty((L.avse_gln_cl_workspace_bytes(Bn, R, C) + 3) // 4, device=x.device, dtype=torch.float32)
+    check(L.avse_gln_cl_fwd_len(Bn, R, C, N, ptr(x), ptr(ldev), int(len_axis), ptr(gamma.float().contiguous()),
+                                ptr(beta.float().contiguous()), float(eps), ptr(res), int(bool(transpose_out)), ptr(y),
+                                ptr(stats), ptr(ws), stream_ptr(x.device)), "avse_gln_cl_fwd_len")
+    return y, stats
+
+
 # ------------------------------------------------------------------------ PReLU -> gLN (avse4)
 
 def prelu_gln_fwd(x, alpha, gamma, beta, eps=1e-8, lengths=None):

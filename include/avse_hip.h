@@ -577,6 +577,21 @@ int avse_gather_nearest_len(int64_t B, int64_t C, int64_t n_in_max, int64_t T, c
                             const int32_t* vlen, const int32_t* tlen, float* out, int64_t out_bs, int64_t out_ts,
                             avse_stream_t stream);
 
+/* ---------------------------------------------------------------- ragged inference batches (DPMamba) ----
+ * Channels-last GroupNorm(1, N) (speechbrain Dual_Computation_Block intra_norm / inter_norm, Dual_Path_Model.norm:
+ * biased variance, eps inside the rsqrt) with a per-row valid extent.  x (B, R, C, N) fp32 contiguous; lengths (device,
+ * B x int32, clamped into the axis): row b is valid for r < n_b with len_axis 0 and for c < n_b with len_axis 1.  The
+ * statistics run over the row's valid elements alone; y = (x - mean) rstd gamma_n + beta_n (+ res, may be null) there
+ * and +0 at every other position; x and res are never loaded at an invalid position.  transpose_out != 0: y and res
+ * are (B, C, R, N).  stats (B, 2) = (mean, rstd), (0, 0) for n_b == 0.  Row b comes out bit for bit (y and stats) as
+ * the call on the row cropped and alone: B = 1, the axis cut to n_b, contiguous.  No atomics; every element of y and
+ * stats is written.  N % 4 == 0 with 16-B aligned tensors takes 16-B accesses, any other N dword ones (same bits).
+ * workspace: avse_gln_cl_workspace_bytes, need not be initialised.  Inference only: there is no backward. */
+int64_t avse_gln_cl_workspace_bytes(int64_t B, int64_t R, int64_t C);
+int avse_gln_cl_fwd_len(int64_t B, int64_t R, int64_t C, int64_t N, const float* x, const int32_t* lengths,
+                        int32_t len_axis, const float* gamma, const float* beta, float eps, const float* res,
+                        int32_t transpose_out, float* y, float* stats, float* workspace, avse_stream_t stream);
+
 /* ---------------------------------------------------------------- LSTM recurrence ----------
  * Replaces the per-step cuDNN/MIOpen LSTM behind nn.LSTM at baseline/avse1/model.py:88 (FusionNet:
  * LSTM(1540 -> 257), batch_first) and baseline/avse2/model.py:101-102 (DPRNN, bidirectional: one call per

@@ -1,0 +1,182 @@
+"""Length-aware batched separation of a ragged DPMamba batch (DPMambaTasNet.forward_ragged, separate_batch,
+DualPathModel.forward_ragged, DualComputationBlock.forward_ragged; tools/mamba_separate.py) against the fp64 oracle on
+each utterance alone.
+
+Reduced model (N = 64, kernel 16, 2 dual-path blocks, chunks of K = 50, 2 speakers), det_init_ seed 93, eval, with and
+without the skip around the intra pass.  Four mixtures 0.1 det_input((t,), 6200 + b) of T = (4000, 2307, 3000, 3008)
+samples: (499, 287, 374, 375) encoder frames in (22, 14, 16, 18) chunks; 375 frames is the row whose tail gap is a
+whole chunk (gap == K), and 3 samples lie past the last frame of utterance 1.  The bar is that of
+tests/test_gpu_fullsize.py: waveform RMS <= 1e-4 max(1, RMS(ref)) and |dSI-SDR| <= 0.01 dB against
+0.1 det_input((t, 2), 6220 + b) as the clean signals.  On the CPU the oracle run on the zero-padded batch misses that
+bar by 148x to 369x for the three shorter utterances: every GroupNorm(1, N) of the dual-path model takes its statistics
+over the whole padded sample.  The oracle runs once per model (module fixture); all GPU work allocates dirty."""
+import importlib.util
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import _dirty
+from oracle import dpmamba_ref
+from oracle.det_init import det_init_, det_input
+from oracle.losses_ref import si_sdr_db
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda"
+KW = dict(N=64, n_dp=2, kernel_size=16, chunk_size=50, n_spk=2)
+T_LEN = (4000, 2307, 3000, 3008)
+K_LEN = tuple((t - 16) // 8 + 1 for t in T_LEN)
+
+
+def errors(est, ref, clean):
+    """(RMS error, its bar, max |dSI-SDR| in dB) of test_gpu_fullsize.check_waveforms; all (T, n_spk)."""
+    est, ref, clean = (torch.as_tensor(np.asarray(a)).double().T for a in (est, ref, clean))
+    rms = float((est - ref).pow(2).mean().sqrt())
+    bar = 1e-4 * max(1.0, float(ref.pow(2).mean().sqrt()))
+    d = float((si_sdr_db(clean, est) - si_sdr_db(clean, ref)).abs().max())
+    return rms, bar, d
+
+
+def padded(mixes, fill):
+    mix = torch.full((len(mixes), max(m.shape[0] for m in mixes)), fill)
+    for b, m in enumerate(mixes):
+        mix[b, :m.shape[0]] = m
+    return mix.to(DEV)
+
+
+@pytest.fixture(scope="module", params=[True, False], ids=["skip", "noskip"])
+def case(request):
+    from avse_challenge_amd import dpmamba as M
+    torch.backends.cuda.matmul.allow_tf32 = False
+    torch.backends.cudnn.allow_tf32 = False
+    torch.set_num_threads(16)
+    mixes = [0.1 * det_input((t,), 6200 + b) for b, t in enumerate(T_LEN)]
+    clean = [0.1 * det_input((t, 2), 6220 + b) for b, t in enumerate(T_LEN)]
+    short = 0.1 * det_input((16,), 6204)                                  # one encoder frame, two chunks
+    m = det_init_(M.DPMambaTasNet(skip_around_intra=request.param, **KW), 93).to(DEV).eval()
+    r = det_init_(dpmamba_ref.DPMambaTasNet(skip_around_intra=request.param, **KW), 93).double().eval()
+    with torch.no_grad():
+        refs = [r(x[None].double())[0].numpy() for x in mixes]          # the oracle on each utterance alone, fp64
+        ref_short = r(short[None].double())[0].numpy()
+    mp = pytest.MonkeyPatch()
+    with _dirty.dirty(mp):
+        out = m.forward_ragged(padded(mixes, 0.0), T_LEN)
+    return dict(m=m, mixes=mixes, clean=clean, refs=refs, out=out, short=short, ref_short=ref_short)
+
+
+def test_chunk_count_is_the_dense_segmentation():
+    from avse_challenge_amd.dpmamba import DualPathModel
+    assert K_LEN == (499, 287, 374, 375)
+    assert [DualPathModel.chunk_count(n, 50) for n in K_LEN + (1,)] == [22, 14, 16, 18, 2]
+    for K in (50, 250):
+        for n in (1, K // 2 - 1, K // 2, K // 2 + 1, K - 1, K, K + 1, 375, 499):
+            seg, gap = DualPathModel._segmentation(torch.zeros(1, 1, n), K)
+            assert DualPathModel.chunk_count(n, K) == seg.shape[3] and 1 <= gap <= K, (K, n)
+    assert DualPathModel._segmentation(torch.zeros(1, 1, 375), 50)[1] == 50
+
+
+def test_a_each_row_matches_the_oracle_on_the_utterance_alone(case):
+    assert case["out"].shape == (4, 4000, 2)
+    for b, t in enumerate(T_LEN):
+        rms, bar, dsdr = errors(case["out"][b, :t].cpu(), case["refs"][b], case["clean"][b])
+        print(f"\nutterance {b}: RMS error {rms:.2e} (bar {bar:.1e}), |dSI-SDR| {dsdr:.2e} dB")
+        assert rms <= bar, f"utterance {b}: RMS waveform error {rms:.3e} > {bar:.1e}"
+        assert dsdr <= 0.01, f"utterance {b}: SI-SDR differs by {dsdr:.4f} dB"
+
+
+def test_b_one_frame_utterance(case, monkeypatch):
+    """A 16-sample utterance (one frame, S = 2 chunks) in the batch: held to the RMS bar."""
+    mixes = case["mixes"] + [case["short"]]
+    with _dirty.dirty(monkeypatch):
+        got = case["m"].forward_ragged(padded(mixes, 0.0), T_LEN + (16,))
+    assert got.shape == (5, 4000, 2) and bool(torch.isfinite(got).all())
+    est, ref = got[4, :16].double().cpu(), torch.from_numpy(case["ref_short"])
+    rms = float((est - ref).pow(2).mean().sqrt())
+    bar = 1e-4 * max(1.0, float(ref.pow(2).mean().sqrt()))
+    print(f"\none-frame utterance: RMS error {rms:.2e} (bar {bar:.1e})")
+    assert rms <= bar and not bool(got[4, 16:].any())
+
+
+def test_c_what_the_padding_holds_is_not_used(case, monkeypatch):
+    with _dirty.dirty(monkeypatch):
+        got = case["m"].forward_ragged(padded(case["mixes"], float("nan")), torch.tensor(T_LEN))
+    assert bool(torch.isfinite(got).all())
+    assert torch.equal(got, case["out"])
+
+
+def test_d_the_tail_is_the_reference_pad(case):
+    assert [t - (8 * (k - 1) + 16) for t, k in zip(T_LEN, K_LEN)] == [0, 3, 0, 0]
+    for b, (t, k) in enumerate(zip(T_LEN, K_LEN)):
+        row, end = case["out"][b], 8 * (k - 1) + 16
+        assert not bool(row[end:].any()) and not bool(row[t:].any())
+        assert bool(row[end - 8:end].any(dim=0).all())                  # the last frame's own hop is there
+        assert not case["refs"][b][end:].any()                           # ... and alone the same samples are 0
+
+
+def test_e_zero_padding_alone_misses_the_bar(case):
+    """Negative control: the dense forward on the zero-padded batch misses bar (a) for the three shorter utterances,
+    so (a) cannot pass by accident of the inputs."""
+    with torch.no_grad():
+        est = case["m"](padded(case["mixes"], 0.0))
+    for b in (1, 2, 3):
+        rms, bar, dsdr = errors(est[b, :T_LEN[b]].cpu(), case["refs"][b], case["clean"][b])
+        print(f"\ndense forward on the padded batch, utterance {b}: RMS {rms:.2e} (bar {bar:.1e}), |dSI-SDR| {dsdr:.2e} dB")
+        assert not (rms <= bar and dsdr <= 0.01)
+
+
+def test_f_separate_batch_returns_the_rows_in_input_order(case, monkeypatch):
+    m, mixes = case["m"], case["mixes"]
+    with _dirty.dirty(monkeypatch):
+        got = m.separate_batch([mixes[0], mixes[1].numpy(), mixes[2], mixes[3].numpy()], batch_size=2)
+    assert len(got) == 4
+    for b, (t, est) in enumerate(zip(T_LEN, got)):
+        assert est.shape == (t, 2) and est.dtype == np.float32
+        rms, bar, dsdr = errors(est, case["refs"][b], case["clean"][b])
+        print(f"\nseparate_batch, utterance {b}: RMS {rms:.2e} (bar {bar:.1e}), |dSI-SDR| {dsdr:.2e} dB")
+        assert rms <= bar and dsdr <= 0.01, (b, rms, bar, dsdr)
+        with torch.no_grad():
+            alone = m(mixes[b][None].to(DEV))[0].cpu()
+        rms, bar, dsdr = errors(est, alone, case["clean"][b])
+        print(f"  vs model(mix[None]): RMS {rms:.2e} (bar {bar:.1e}), |dSI-SDR| {dsdr:.2e} dB")
+        assert rms <= bar and dsdr <= 0.01, (b, rms, bar, dsdr)
+    with pytest.raises(ValueError):
+        m.separate_batch([mixes[0], mixes[1][:15]], batch_size=2)         # shorter than one encoder window
+    with pytest.raises(ValueError):
+        m.forward_ragged(padded(mixes, 0.0), (4000, 15, 3000, 3008))
+    with pytest.raises(RuntimeError), torch.autocast("cuda", dtype=torch.bfloat16):
+        m.forward_ragged(padded(mixes, 0.0), T_LEN)
+
+
+def test_g_the_tool_separates_a_directory(case, tmp_path):
+    """tools/mamba_separate.py (separate_dir) with a DPMamba model on three mixtures: the files test_g of
+    tests/test_gpu_mamba_ragged.py expects, each the peak-normalised separate_batch estimate of what the tool read to
+    the PCM_16 step; an existing output is left alone and a second run finds nothing to do."""
+    from avse_challenge_amd import ckpt_io
+    here = os.path.dirname(os.path.abspath(__file__))
+    spec = importlib.util.spec_from_file_location("mamba_separate", os.path.join(here, "..", "tools", "mamba_separate.py"))
+    tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tool)
+    mix, out, s1, s2 = (str(tmp_path / d) for d in ("mix", "out", "s1", "s2"))
+    for d in (mix, out, s1, s2):
+        os.mkdir(d)
+    for b, x in enumerate(case["mixes"][:3]):
+        ckpt_io.write_wav(os.path.join(mix, f"u{b}.wav"), x.numpy(), 8000)
+        for k, d in enumerate((s1, s2)):
+            ckpt_io.write_wav(os.path.join(d, f"u{b}.wav"), case["clean"][b][:, k].numpy(), 8000)
+    for k in (1, 2):                                                      # there already: not redone
+        ckpt_io.write_wav(os.path.join(out, f"itemu2_source{k}hat.wav"), np.zeros(10), 8000)
+    assert tool.separate_dir(case["m"], mix, out, batch_size=2, target_dirs=[s1, s2]) == ["u0", "u1"]
+    assert sorted(os.listdir(out)) == sorted([f"itemu{b}_source{k}hat.wav" for b in range(3) for k in (1, 2)] +
+                                             ["test_results.csv"])
+    assert ckpt_io.read_wav(os.path.join(out, "itemu2_source1hat.wav"))[0].shape == (10,)
+    read = [tool.load_wav(os.path.join(mix, f"u{b}.wav"), 8000)[0] for b in (0, 1)]
+    for b, est in enumerate(case["m"].separate_batch(read, batch_size=2)):
+        for k in (0, 1):
+            wav, sr = ckpt_io.read_wav(os.path.join(out, f"itemu{b}_source{k + 1}hat.wav"))
+            assert sr == 8000 and wav.shape == (T_LEN[b],)
+            assert float(np.abs(wav - est[:, k] / np.max(np.abs(est[:, k]))).max()) <= 1.5 / 32768
+    rows = open(os.path.join(out, "test_results.csv")).read().strip().splitlines()
+    assert rows[0] == "snt_id,si-snr,si-snr_i" and [r.split(",")[0] for r in rows[1:]] == ["u0", "u1", "avg"]
+    assert all(np.isfinite(float(v)) for r in rows[1:] for v in r.split(",")[1:])
+    assert tool.find_mixtures(mix, out, 2) == [] and tool.separate_dir(case["m"], mix, out, batch_size=2) == []

@@ -1,19 +1,20 @@
-"""Separate a directory of mixture wavs with a Mamba-TasNet checkpoint in ragged batches on the GPU: the counterpart of
-the reference's save_results / save_audio (train_wsj0mix.py:503-642), which separate and score one utterance per step.
+"""Separate a directory of mixture wavs with a Mamba-TasNet or DPMamba checkpoint in ragged batches on the GPU: the
+counterpart of the reference's save_results / save_audio (train_wsj0mix.py:503-642), which separate and score one
+utterance per step.
 
     python tools/mamba_separate.py --hparams results/.../hyperparams.yaml --ckpt-dir results/.../save \\
         --mix wsj0-mix/2speakers/wav8k/min/tt/mix --out separated/ \\
-        [--targets .../tt/s1 .../tt/s2] [--batch-size 16 --max-pad-ratio 1.25 --sample-rate 8000]
+        [--targets .../tt/s1 .../tt/s2] [--batch-size B --max-pad-ratio 1.25 --sample-rate 8000]
 
 For every `<id>.wav` in --mix it writes `<out>/item<id>_source<k>hat.wav` (k = 1 .. n_spk; PCM_16, each source divided
 by its peak as save_audio does) unless all of an utterance's files exist already.  Utterances are sorted by length
-and cut into batches by avse4.plan_ragged_batches; each batch is one MambaTasNet.forward_ragged call
-(MambaTasNet.separate_batch).  With --targets (one directory per speaker, holding `<id>.wav` too) it also writes
-`<out>/test_results.csv` with the columns snt_id, si-snr, si-snr_i and a final avg row, from losses.si_snr_pit on the
-unnormalised estimates, for the utterances separated in this run.  The reference's sdr / sdr_i columns need mir_eval's
-bss_eval_sources, which this project does not depend on: they are left out.
-
-DPMamba checkpoints are refused: its ragged path is not built.
+and cut into batches by avse4.plan_ragged_batches; each batch is one forward_ragged call of the model the hparams
+describe (MambaTasNet.separate_batch, DPMambaTasNet.separate_batch).  With --targets (one directory per speaker,
+holding `<id>.wav` too) it also writes `<out>/test_results.csv` with the columns snt_id, si-snr, si-snr_i and a final
+avg row, from losses.si_snr_pit on the unnormalised estimates, for the utterances separated in this run.  The
+reference's sdr / sdr_i columns need mir_eval's bss_eval_sources, which this project does not depend on: they are left
+out.  --batch-size defaults to the fastest measured size of the model: 16 for Mamba-TasNet, 4 for DPMamba (DESIGN
+§4.11, §4.13).
 """
 import argparse
 import csv
@@ -27,6 +28,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from avse_challenge_amd import ckpt_io, losses  # noqa: E402
 
 CSV_COLUMNS = ["snt_id", "si-snr", "si-snr_i"]
+DEFAULT_BATCH_SIZE = {"MambaTasNet": 16, "DPMambaTasNet": 4}
 
 
 def out_paths(out_dir, snt_id, n_spk):
@@ -91,10 +93,7 @@ def separate_dir(model, mix_dir, out_dir, batch_size=16, max_pad_ratio=1.25, sam
 
 
 def load_model(hparams, ckpt_dir, device="cuda"):
-    from avse_challenge_amd import mamba_tasnet
-    model = ckpt_io.model_from_hparams(ckpt_io.read_hparams(hparams))
-    if not isinstance(model, mamba_tasnet.MambaTasNet):
-        raise SystemExit("mamba_separate: only Mamba-TasNet has a ragged path (DPMamba's is not built)")
+    model = ckpt_io.model_from_hparams(ckpt_io.read_hparams(hparams))     # a MambaTasNet or a DPMambaTasNet
     ckpt = ckpt_dir if os.path.isfile(os.path.join(ckpt_dir, "CKPTMETA.yaml")) \
         else ckpt_io.find_speechbrain_checkpoint(ckpt_dir)
     if ckpt is None:
@@ -110,14 +109,15 @@ def main(argv=None):
     ap.add_argument("--mix", required=True, help="directory of the mixture wavs")
     ap.add_argument("--out", required=True, help="output directory")
     ap.add_argument("--targets", nargs="*", default=None, help="one directory of clean wavs per speaker")
-    ap.add_argument("--batch-size", type=int, default=16)
+    ap.add_argument("--batch-size", type=int, default=None, help="default: 16 (Mamba-TasNet), 4 (DPMamba)")
     ap.add_argument("--max-pad-ratio", type=float, default=1.25)
     ap.add_argument("--sample-rate", type=int, default=8000)
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("mamba_separate needs the GPU")
     model = load_model(a.hparams, a.ckpt_dir)
-    written = separate_dir(model, a.mix, a.out, a.batch_size, a.max_pad_ratio, a.sample_rate, a.targets or None)
+    batch_size = a.batch_size or DEFAULT_BATCH_SIZE[type(model).__name__]
+    written = separate_dir(model, a.mix, a.out, batch_size, a.max_pad_ratio, a.sample_rate, a.targets or None)
     print(f"{len(written)} utterances -> {a.out}")
 
 

@@ -1,15 +1,15 @@
-"""Utterances/s of Mamba-TasNet separation over a ragged set: the loop of `model(mix[None])` (one utterance per forward,
-as the reference's save_results scores WSJ0-mix) against `separate_batch` on avse4.plan_ragged_batches at several batch
-sizes, same build, same process.
+"""Utterances/s of Mamba-TasNet or DPMamba separation over a ragged set: the loop of `model(mix[None])` (one utterance
+per forward, as the reference's save_results scores WSJ0-mix) against `separate_batch` on avse4.plan_ragged_batches at
+several batch sizes, same build, same process.
 
     python tools/mamba_separate_bench.py [--utterances 64 --min-s 3 --max-s 9 --batch-sizes 4,16,32 --repeats 2] \\
-        [--size L --out profiles/mamba_separate_bench.json]
+        [--model mamba|dpmamba --size L --out profiles/mamba_separate_bench.json]
 
-A seeded synthetic set (noise at 8 kHz, lengths uniform in [min-s, max-s]), Mamba-TasNet-L with det_init_ weights in
-eval mode, fp32.  Every arm gets one untimed pass over the whole set (allocator, code objects), then `repeats` timed
-passes between two device events; host-side padding, the upload and the download are inside the timed span for both
-arms, as a tool run pays them.  Arms alternate within a repeat.  Prints one JSON line.  A run without a GPU fails;
-nothing here falls back.
+A seeded synthetic set (noise at 8 kHz, lengths uniform in [min-s, max-s]), Mamba-TasNet-L (or DPMamba-L: --model
+dpmamba) with det_init_ weights in eval mode, fp32.  Every arm gets one untimed pass over the whole set (allocator,
+code objects), then `repeats` timed passes between two device events; host-side padding, the upload and the download
+are inside the timed span for both arms, as a tool run pays them.  Arms alternate within a repeat.  Prints one JSON
+line.  A run without a GPU fails; nothing here falls back.
 """
 import argparse
 import json
@@ -21,10 +21,12 @@ import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
-from avse_challenge_amd import avse4, mamba_tasnet  # noqa: E402
+from avse_challenge_amd import avse4, dpmamba, mamba_tasnet  # noqa: E402
 from oracle.det_init import det_init_  # noqa: E402
 
 SAMPLE_RATE = 8000
+MODELS = {"mamba": ("Mamba-TasNet", mamba_tasnet.MambaTasNet, mamba_tasnet.MAMBA_TASNET_SIZES),
+          "dpmamba": ("DPMamba", dpmamba.DPMambaTasNet, dpmamba.DPMAMBA_SIZES)}
 
 
 def synthetic_set(n, min_s, max_s, seed=0):
@@ -50,6 +52,7 @@ def main(argv=None):
     ap.add_argument("--batch-sizes", default="4,16,32")
     ap.add_argument("--max-pad-ratio", type=float, default=1.25)
     ap.add_argument("--repeats", type=int, default=2)
+    ap.add_argument("--model", default="mamba", choices=sorted(MODELS))
     ap.add_argument("--size", default="L", choices=sorted(mamba_tasnet.MAMBA_TASNET_SIZES))
     ap.add_argument("--out", default=None, help="also write the line to this file")
     a = ap.parse_args(argv)
@@ -59,7 +62,8 @@ def main(argv=None):
     torch.backends.cudnn.allow_tf32 = False
     mixes = synthetic_set(a.utterances, a.min_s, a.max_s)
     lengths = [m.shape[0] for m in mixes]
-    model = det_init_(mamba_tasnet.MambaTasNet(**mamba_tasnet.MAMBA_TASNET_SIZES[a.size]), 0).to("cuda").eval()
+    name, cls, table = MODELS[a.model]
+    model = det_init_(cls(**table[a.size]), 0).to("cuda").eval()
     sizes = [int(v) for v in a.batch_sizes.split(",")]
     plans = {bs: avse4.plan_ragged_batches(lengths, bs, a.max_pad_ratio) for bs in sizes}
 
@@ -77,7 +81,7 @@ def main(argv=None):
     for _ in range(a.repeats):
         for k, fn in arms.items():
             ms[k].append(_timed_ms(fn))
-    rec = {"metric": "mamba_separate_utterances_per_s", "unit": "utterances/s", "model": f"Mamba-TasNet-{a.size}",
+    rec = {"metric": "mamba_separate_utterances_per_s", "unit": "utterances/s", "model": f"{name}-{a.size}",
            "utterances": a.utterances, "seconds_of_audio": round(sum(lengths) / SAMPLE_RATE, 1), "min_s": a.min_s,
            "max_s": a.max_s, "max_pad_ratio": a.max_pad_ratio, "repeats": a.repeats,
            "device": torch.cuda.get_device_name(0), "arms": {}}
