@@ -22,6 +22,7 @@ import torch.nn.functional as F
 from . import kernels as K
 from .layers import (DilatedConv2d, HipLSTM, LipConv3d, PointwiseConv2d, PReLU, TrunkConv2d, bn_act,
                      bn_act_pool_frames, conv1x1_to4, maxpool3d, time_conv1d, time_major_4d)
+from .ragged import Lengths, as_lengths, pad_stack, run_planned
 
 STFT_BINS, NUM_STFT_FRAMES, NUM_FRAMES, SAMPLES = 257, 376, 75, 48000
 
@@ -162,11 +163,6 @@ class _TCN(nn.Module):                    # utils/nn.py:106-128 (extract_feats=T
         return self.tcn_trunk.forward_ragged(x.contiguous(), lengths)
 
 
-def _valid_steps(lengths, n):
-    """(B, n) bool: step t of sample b is one of its own (t < lengths[b])."""
-    return torch.arange(n, device=lengths.dev.device)[None, :] < lengths.dev[:, None]
-
-
 class VisualFeatNet(nn.Module):           # model.py:17-58
     def __init__(self):
         super().__init__()
@@ -208,8 +204,8 @@ class VisualFeatNet(nn.Module):           # model.py:17-58
         if self.training:
             raise RuntimeError("VisualFeatNet.forward_ragged is an inference path: call .eval() first")
         Bn, Tn = lips.shape[0], lips.shape[2]
-        vl = K._lengths(vis_lengths, Bn, Tn, lips.device, "VisualFeatNet.forward_ragged")
-        valid = _valid_steps(vl, Tn)
+        vl = as_lengths(vis_lengths, Bn, Tn, lips.device, "VisualFeatNet.forward_ragged")
+        valid = vl.valid(Tn)
         lips = torch.where(valid[:, None, :, None, None], lips, lips.new_zeros(()))
         conv, bn, act, pool = self.frontend3D
         x = conv(lips)
@@ -277,7 +273,7 @@ class AudioFeatNet(nn.Module):            # model.py:181-267 (5 dilated 5x5 conv
         if self.training:
             raise RuntimeError("AudioFeatNet.forward_ragged is an inference path: call .eval() first")
         T, Fb = spec.shape[2], spec.shape[3]
-        fl = K._lengths(frame_lengths, spec.shape[0], T, spec.device, "AudioFeatNet.forward_ragged")
+        fl = as_lengths(frame_lengths, spec.shape[0], T, spec.device, "AudioFeatNet.forward_ragged")
         x = bn_act(spec.contiguous(), self.bn0, lengths=fl)
         if self.channels_last:
             x = x.contiguous(memory_format=torch.channels_last)
@@ -445,11 +441,11 @@ class AVNet(nn.Module):
             raise RuntimeError("AVNet.forward_ragged runs in fp32: leave the autocast region")
         spec = inp["noisy_audio_spec"]
         Bn, T = spec.shape[0], spec.shape[2]
-        fl = K._lengths(frame_lengths, Bn, T, spec.device, "AVNet.forward_ragged (frame_lengths)")
+        fl = as_lengths(frame_lengths, Bn, T, spec.device, "AVNet.forward_ragged (frame_lengths)")
         vl = None
         if not self.a_only:
             lips = inp["lip_images"]
-            vl = K._lengths(vis_lengths, Bn, lips.shape[2], spec.device, "AVNet.forward_ragged (vis_lengths)")
+            vl = as_lengths(vis_lengths, Bn, lips.shape[2], spec.device, "AVNet.forward_ragged (vis_lengths)")
         side = None if self.a_only else _branch_stream(spec.device)
         if side is not None:
             main = torch.cuda.current_stream(spec.device)
@@ -478,10 +474,9 @@ class AVNet(nn.Module):
         """enhance() for a list of utterances of different lengths (test.py:58-89 walks them one at a time): items are
         (noisy_wave, lips) pairs or dicts with "noisy_audio" and "lip_images" -- a 1-D waveform and the (3, Tv, H, W)
         lip frames (uint8 as stored, or float; all items alike; None / absent for the audio-only net).  They are cut
-        into batches by avse4.plan_ragged_batches (sorted by length, at most batch_size items, padded / useful samples
+        into batches by ragged.plan_ragged_batches (sorted by length, at most batch_size items, padded / useful samples
         <= max_pad_ratio); each batch is one padded upload, the length-aware STFT, forward_ragged, the length-aware
         iSTFT and one download.  Returns the estimates in the order of `items`, numpy float32 (T_b,)."""
-        from .avse4 import plan_ragged_batches
         if self.training:
             raise RuntimeError("AVNet.enhance_batch is an inference path: call .eval() first")
         if torch.is_autocast_enabled():
@@ -507,29 +502,21 @@ class AVNet(nn.Module):
         if clips and any(c.shape[2:] != clips[0].shape[2:] or c.dtype != clips[0].dtype for c in clips):
             raise ValueError("enhance_batch: all lip clips must share their frame size and dtype")
         dev = next(self.parameters()).device
-        out = [None] * len(items)
-        for batch in plan_ragged_batches([w.shape[0] for w in waves], batch_size, max_pad_ratio):
-            tl = [waves[i].shape[0] for i in batch]
-            audio = np.zeros((len(batch), max(tl)), np.float32)
-            for b, i in enumerate(batch):
-                audio[b, :tl[b]] = waves[i]
-            wl = K.Lengths(tl, dev)
+
+        def run(batch):
+            audio, tl = pad_stack(waves, 0, batch)
+            wl = Lengths(tl, dev)
             inp, vl = {}, None
             if not self.a_only:
-                tv = [clips[i].shape[1] for i in batch]
-                video = np.zeros((len(batch), 3, max(tv)) + clips[0].shape[2:], clips[0].dtype)
-                for b, i in enumerate(batch):
-                    video[b, :, :tv[b]] = clips[i]
+                video, tv = pad_stack(clips, 1, batch)
                 inp["lip_images"] = torch.from_numpy(video).to(dev)
-                vl = K.Lengths(tv, dev)
+                vl = Lengths(tv, dev)
             mag, spec = K.stft(torch.from_numpy(audio).to(dev), return_complex=True, lengths=wl)
             inp["noisy_audio_spec"] = mag.unsqueeze(1)
-            fl = K.Lengths([K.stft_frames(t) for t in tl], dev)
-            pred = self.forward_ragged(inp, fl, vl)[:, 0]
+            pred = self.forward_ragged(inp, wl.map(K.stft_frames), vl)[:, 0]
             est = K.istft(pred, spec, max(tl), lengths=wl).cpu().numpy()
-            for b, i in enumerate(batch):
-                out[i] = est[b, :tl[b]].copy()
-        return out
+            return [est[b, :t].copy() for b, t in enumerate(tl)]
+        return run_planned([w.shape[0] for w in waves], batch_size, max_pad_ratio, run)
 
 
 def load_lightning_state_dict(model, ckpt_state_dict):

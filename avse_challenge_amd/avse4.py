@@ -23,6 +23,7 @@ from . import kernels as K
 from . import losses
 from .layers import (LipConv3d, PointwiseConv2d, TrunkConv2d, _PReLUFn, bn_act, bn_act_pool_frames, dwconv1d,
                      dwconv_prelu_gln, maxpool3d, prelu_gln)
+from .ragged import Lengths, as_lengths, pad_stack, plan_ragged_batches  # noqa: F401 (plan_ragged_batches: re-export)
 
 NORM_MEAN, NORM_STD = 0.4161, 0.1688
 
@@ -107,10 +108,6 @@ def _pw(conv, x, dy_planes=False):
     """1x1 Conv1d without bias: (Cout, Cin) @ (B, Cin, K).  dy_planes: the output's consumer hands back its gradient as
     split planes (prelu_gln(planes_bwd=True)); the backward raises if they are missing."""
     return _PointwiseFn.apply(conv.weight[:, :, 0], x, dy_planes)
-
-
-def _as_lengths(lengths, device):
-    return lengths if isinstance(lengths, K.Lengths) else K.Lengths(lengths, device)
 
 
 _INTERP = {}
@@ -269,8 +266,7 @@ class TemporalConvNet(nn.Module):
         absmax pass reads keeps exact zeros there, so sample b's mask equals forward() on it alone; the
         mask is 0 past lengths[b]."""
         dev = x.device
-        kvalid = (torch.arange(x.shape[-1], device=dev) < lengths.dev[:, None])[:, None]
-        vvalid = (torch.arange(visual.shape[1], device=dev) < vis_lengths.dev[:, None])[:, None]
+        kvalid, vvalid = lengths.valid(x.shape[-1])[:, None], vis_lengths.valid(visual.shape[1])[:, None]
         visual = visual.transpose(1, 2)
         for vc in self.visual_conv:
             visual = vc.forward_ragged(visual, vvalid, vis_lengths)
@@ -344,13 +340,12 @@ class Separator(nn.Module):
         of mixture holds, NaN and Inf included, is not used."""
         L, hop = self.encoder.L, self.encoder.L // 2
         dev = mixture.device
-        tl = _as_lengths(lengths, dev).checked(mixture.shape[0], mixture.shape[-1], "forward_ragged (lengths)")
+        tl = as_lengths(lengths, mixture.shape[0], mixture.shape[-1], dev, "forward_ragged (lengths)")
         if min(tl.host) < L:
             raise ValueError(f"forward_ragged: every utterance needs at least {L} samples, got {min(tl.host)}")
-        kl = K.Lengths([(t - L) // hop + 1 for t in tl.host], dev)
-        vl = _as_lengths(vis_lengths, dev).checked(visual.shape[0], visual.shape[1], "forward_ragged (vis_lengths)")
-        tvalid = (torch.arange(mixture.shape[-1], device=dev) < tl.dev[:, None])[:, None]
-        kvalid = (torch.arange((mixture.shape[-1] - L) // hop + 1, device=dev) < kl.dev[:, None])[:, None]
+        kl = tl.map(lambda t: (t - L) // hop + 1)
+        vl = as_lengths(vis_lengths, visual.shape[0], visual.shape[1], dev, "forward_ragged (vis_lengths)")
+        tvalid, kvalid = tl.valid(mixture.shape[-1])[:, None], kl.valid((mixture.shape[-1] - L) // hop + 1)[:, None]
         # the frame past an utterance's last still overlaps valid samples: selected away, with the padding frames
         w = torch.where(kvalid, self.encoder(torch.where(tvalid, mixture.float(), 0.0)), 0.0)
         est = self.decoder(w, self.separator.forward_ragged(w, visual, kl, vl))
@@ -425,8 +420,8 @@ class VisualFrontend(nn.Module):
         """forward for a padded batch of clips with vis_lengths[b] valid frames (inference): the normalised frames past
         them are selected to 0 -- what the Conv3d's own zero padding in time is for a clip alone -- and so are the
         features there.  Frames are independent after the Conv3d, so clip b's valid features equal forward() on it."""
-        vl = _as_lengths(vis_lengths, x.device).checked(x.shape[0], x.shape[2], "VisualFrontend.forward_ragged")
-        valid = torch.arange(x.shape[2], device=x.device) < vl.dev[:, None]                  # (B, Tv)
+        vl = as_lengths(vis_lengths, x.shape[0], x.shape[2], x.device, "VisualFrontend.forward_ragged")
+        valid = vl.valid(x.shape[2])                                                         # (B, Tv)
         y = self._features(torch.where(valid[:, None, :, None, None], (x.float() - NORM_MEAN) / NORM_STD, 0.0))
         return torch.where(valid[:, :, None], y, 0.0)
 
@@ -503,13 +498,8 @@ class AVSE4BaselineModule(nn.Module):
         dev = next(self.parameters()).device
         noisy = [np.asarray(d["noisy_audio"], dtype=np.float32) for d in items]
         vis = [np.asarray(d["vis_feat"], dtype=np.float32) for d in items]
-        tl, vl = [a.shape[-1] for a in noisy], [v.shape[1] for v in vis]
-        audio = np.zeros((len(items), noisy[0].shape[0], max(tl)), np.float32)
-        video = np.zeros((len(items), 1, max(vl)) + vis[0].shape[2:], np.float32)
-        for b, (a, v) in enumerate(zip(noisy, vis)):
-            audio[b, :, :tl[b]] = a
-            video[b, :, :vl[b]] = v
-        vlen = K.Lengths(vl, dev)
+        (audio, tl), (video, vl) = pad_stack(noisy, -1), pad_stack(vis, 1)
+        vlen = Lengths(vl, dev)
         feats = self.visual_frontend.forward_ragged(torch.from_numpy(video).to(dev), vlen)
         est = self.model.forward_ragged(torch.from_numpy(audio).to(dev), feats, tl, vlen).cpu().numpy()
         out = []
@@ -519,26 +509,3 @@ class AVSE4BaselineModule(nn.Module):
             out.append((np.asarray(d.get("clean")) if d.get("clean") is not None else None,
                         np.asarray(d["noisy_audio"]), e))
         return out
-
-
-def plan_ragged_batches(lengths, batch_size, max_pad_ratio=1.25):
-    """Batches for enhance_batch: the indices of `lengths` sorted by length and cut greedily so that a batch holds at
-    most batch_size items and its padded size max(len) * n stays within max_pad_ratio of its useful size sum(len).
-    Every index appears exactly once; an item no neighbour fits with is a batch of its own (ratio 1).  Host code; the
-    ratio is a setting, not a claim about speed."""
-    if batch_size < 1 or max_pad_ratio < 1.0:
-        raise ValueError("plan_ragged_batches: batch_size >= 1 and max_pad_ratio >= 1")
-    lengths = [int(v) for v in lengths]
-    if any(v < 1 for v in lengths):
-        raise ValueError("plan_ragged_batches: lengths must be positive")
-    batches, cur, total = [], [], 0
-    for i in sorted(range(len(lengths)), key=lambda j: (lengths[j], j)):
-        n = lengths[i]                                       # ascending: the newcomer is the batch's longest
-        if cur and (len(cur) == batch_size or n * (len(cur) + 1) > max_pad_ratio * (total + n)):
-            batches.append(cur)
-            cur, total = [], 0
-        cur.append(i)
-        total += n
-    if cur:
-        batches.append(cur)
-    return batches

@@ -25,7 +25,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import kernels as Kn
-from .mamba_tasnet import Decoder, Encoder, MambaBlocksSequential, MambaTasNet, _autocast_dtype
+from .mamba_tasnet import Decoder, Encoder, MambaBlocksSequential, RaggedSeparation
+from .ragged import as_lengths
 
 # hparams/WSJ0Mix/dpmamba_{XS,S,M,L}.yaml: N_encoder_out = out_channels, n_dp, skip_around_intra
 DPMAMBA_SIZES = {"XS": dict(N=128, n_dp=8, skip_around_intra=False), "S": dict(N=256, n_dp=8, skip_around_intra=False),
@@ -66,11 +67,11 @@ class DualComputationBlock(nn.Module):
     @torch.no_grad()
     def forward_ragged(self, x, chunk_counts, inter_lengths):
         """forward() for a zero-padded ragged batch (inference, fp32): row b of x (B, S, K, N) holds chunk_counts[b]
-        chunks and +0 after them; chunk_counts (B) and inter_lengths (B K: each count K times) are int32 device tensors
-        made once per forward.  The intra blocks run on every chunk (chunks are independent; an all-zero chunk stays
-        finite), the inter blocks over each row's own chunks (MambaBlocksSequential.forward_ragged), and both norms
-        take their statistics over the row's own chunks alone and write +0 past them (kernels.gln_cl_fwd); the inter
-        norm's store is the transpose back and the final sum."""
+        chunks and +0 after them; chunk_counts (a ragged.Lengths of B counts) and inter_lengths (an int32 device tensor
+        of B K entries: each count K times) are made once per forward.  The intra blocks run on every chunk (chunks are
+        independent; an all-zero chunk stays finite), the inter blocks over each row's own chunks
+        (MambaBlocksSequential.forward_ragged), and both norms take their statistics over the row's own chunks alone and
+        write +0 past them (kernels.gln_cl_fwd); the inter norm's store is the transpose back and the final sum."""
         B, S, K, N = x.shape
         intra = self.intra_mdl(x.reshape(B * S, K, N)).view(B, S, K, N)
         intra = Kn.gln_cl_fwd(intra, self.intra_norm.weight, self.intra_norm.bias, self.intra_norm.eps, chunk_counts, 0,
@@ -140,28 +141,24 @@ class DualPathModel(nn.Module):
 
     @torch.no_grad()
     def forward_ragged(self, x, frame_lengths):             # [B, N, L_max] -> [spks, B, N, L_max]
-        """forward() for a zero-padded ragged batch (inference, fp32): row b of x holds frame_lengths[b] (a sequence of
-        host integers in [1, L_max]) frames and 0 after them.  Chunk s covers the same frames whatever the length, so a
-        row's first chunk_count(L_b, K) chunks of the dense segmentation of the L_max batch are the chunks it has
-        alone; every GroupNorm(1, N) takes its statistics over the row's own frames or chunks.  The tail runs dense:
-        the chunks past a row's own only reach frames >= L_b + gap_b, which the caller drops.  Frames from L_b on of
-        the result are not meaningful."""
-        host = [int(v) for v in (frame_lengths.tolist() if hasattr(frame_lengths, "tolist") else frame_lengths)]
+        """forward() for a zero-padded ragged batch (inference, fp32): row b of x holds frame_lengths[b] (the forward's
+        ragged.Lengths, or a sequence; in [1, L_max]) frames and 0 after them.  Chunk s covers the same frames whatever
+        the length, so a row's first chunk_count(L_b, K) chunks of the dense segmentation of the L_max batch are the
+        chunks it has alone; every GroupNorm(1, N) takes its statistics over the row's own frames or chunks.  The tail
+        runs dense: the chunks past a row's own only reach frames >= L_b + gap_b, which the caller drops.  Frames from
+        L_b on of the result are not meaningful."""
         B, N, L = x.shape
-        if len(host) != B or min(host) < 1 or max(host) > L:
-            raise ValueError(f"forward_ragged: {B} frame counts in [1, {L}], got {host}")
         K, P = self.K, self.K // 2
-        counts = [self.chunk_count(n, K) for n in host]
-        f_len = torch.tensor(host, dtype=torch.int32, device=x.device)      # once per forward, for every layer
-        c_len = torch.tensor(counts, dtype=torch.int32, device=x.device)
-        i_len = c_len.repeat_interleave(K)
+        f_len = as_lengths(frame_lengths, B, L, x.device, "forward_ragged")
+        c_len = f_len.map(lambda n: self.chunk_count(n, K))                 # once per forward, for every layer
+        i_len = c_len.dev.repeat_interleave(K)
         x = Kn.gln_cl_fwd(x.transpose(1, 2).contiguous()[:, None], self.norm.weight, self.norm.bias, self.norm.eps,
                           f_len, 1)[0][:, 0]                # (B, L, N), +0 from frame L_b on
         x = F.linear(x, self.conv1d.weight[:, :, 0])        # no bias: the padding stays 0
         gap = K - (P + L % K) % K
         x = F.pad(x, (0, 0, P, gap + P))                    # _segmentation, channels-last: -> (B, S, K, N)
         x = torch.stack([x[:, :-P].reshape(B, -1, K, N), x[:, P:].reshape(B, -1, K, N)], dim=2).view(B, -1, K, N)
-        assert x.shape[1] == max(counts)
+        assert x.shape[1] == max(c_len.host)
         for blk in self.dual_mdl:
             x = blk.forward_ragged(x, c_len, i_len)
         x = self.conv2d(self.prelu(x.permute(0, 3, 2, 1)))  # [B, N*spks, K, S]
@@ -171,8 +168,10 @@ class DualPathModel(nn.Module):
         return self.activation(x.view(B, self.num_spks, N, L)).transpose(0, 1)
 
 
-class DPMambaTasNet(nn.Module):
+class DPMambaTasNet(RaggedSeparation, nn.Module):
     """Encoder / DualPathModel(MambaBlocksSequential intra + inter) / Decoder (train_wsj0mix.py:86-111)."""
+
+    zero_encoder_padding = True     # forward_ragged: DualPathModel's GroupNorms read the encoder output's padding frames
 
     def __init__(self, N=512, n_dp=16, skip_around_intra=True, kernel_size=16, chunk_size=250, n_spk=2,
                  n_mamba_dp=2, d_state=16, expand=2, d_conv=4):
@@ -192,45 +191,3 @@ class DPMambaTasNet(nn.Module):
         if T > est.shape[1]:
             return F.pad(est, (0, 0, 0, T - est.shape[1]))
         return est[:, :T, :]
-
-    @torch.no_grad()
-    def forward_ragged(self, mix, lengths):
-        """forward() for a batch of mixtures of different lengths in one pass (inference, fp32), as
-        MambaTasNet.forward_ragged: mix (B, T_max) holds utterance b in its first lengths[b] samples -> (B, T_max,
-        n_spk) whose row b holds forward(mix[b:b+1, :lengths[b]]) in its first lengths[b] samples and 0 after them.
-        What mix holds past an utterance is not used.
-
-        Utterance b has L_b = (T_b - k) // hop + 1 encoder frames.  The encoder output is set to 0 from frame L_b on (a
-        frame there would hold samples of the utterance's last hop), the masking network runs its length-aware path
-        (DualPathModel.forward_ragged), and the masked encoder output is selected to 0 from frame L_b on before the
-        decoder's overlap-add.  Samples from (L_b - 1) hop + k on are 0, as they are alone."""
-        Kn._need_gpu(mix)
-        if _autocast_dtype() is not None:
-            raise RuntimeError("DPMambaTasNet.forward_ragged runs in fp32 (the bf16 autocast path is not built)")
-        k, hop = self.encoder.conv1d.kernel_size[0], self.encoder.conv1d.stride[0]
-        host = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
-        B, T = mix.shape
-        if len(host) != B or max(host) > T:
-            raise ValueError(f"forward_ragged: {B} lengths of at most {T} samples, got {host}")
-        if min(host) < k:
-            raise ValueError(f"forward_ragged: every utterance needs at least one encoder window of {k} samples, got "
-                             f"{min(host)}")
-        dev = mix.device
-        frames = [(t - k) // hop + 1 for t in host]
-        t_len = torch.tensor(host, device=dev)
-        f_len = torch.tensor(frames, device=dev)
-        zero = mix.new_zeros(())
-        t_idx = torch.arange(T, device=dev)
-        mix = torch.where(t_idx[None, :] < t_len[:, None], mix, zero)     # a select: NaN in the padding is dropped
-        mix_w = self.encoder(mix)                                         # (B, N, L_max)
-        f_ok = torch.arange(mix_w.shape[-1], device=dev)[None, :] < f_len[:, None]            # (B, L_max)
-        mix_w = torch.where(f_ok[:, None, :], mix_w, zero)
-        est_mask = self.masknet.forward_ragged(mix_w, frames)
-        sep_h = torch.where(f_ok[None, :, None, :], mix_w.unsqueeze(0) * est_mask, zero)
-        est = torch.stack([self.decoder(sep_h[i]) for i in range(self.num_spks)], dim=-1)
-        est = F.pad(est, (0, 0, 0, T - est.shape[1])) if T > est.shape[1] else est[:, :T, :]
-        t_ok = t_idx[None, :] < ((f_len - 1) * hop + k)[:, None]
-        return torch.where(t_ok[:, :, None], est, zero)
-
-    # the list -> length-planned padded batches -> forward_ragged loop needs nothing of the model but forward_ragged
-    separate_batch = MambaTasNet.separate_batch

@@ -10,6 +10,7 @@ import torch
 from . import _lib
 from ._lib import (AVSE_BF16, AVSE_F32, ScanBwdArgs, ScanFwdArgs, ScanFwdStateArgs, SsmStepArgs, check, ptr,
                    stream_ptr)
+from .ragged import Lengths, as_lengths  # noqa: F401 (kernels.Lengths stays a name for ragged.Lengths)
 
 NSTATE = 16
 
@@ -139,25 +140,12 @@ def _ssm_state_arg(t, b, d, dev, what):
     return t
 
 
-def _row_lengths(lengths, batch, device, what):
-    """The int32 device tensor of a ragged batch's `batch` row lengths (avse_scan_fwd_len, avse_cconv_fwd_len): an int32
-    tensor on the device is taken as it is, a sequence is uploaded.  The kernels clamp each value to [0, seqlen], so no
-    value is read back here."""
-    if not torch.is_tensor(lengths):
-        lengths = torch.tensor([int(v) for v in lengths], dtype=torch.int32, device=device)
-    if lengths.dtype != torch.int32 or lengths.device != device or tuple(lengths.shape) != (batch,) \
-            or not lengths.is_contiguous():
-        raise ValueError(f"{what}: lengths must be {batch} int32 values on {device} (or a sequence), got "
-                         f"{tuple(lengths.shape)} {lengths.dtype} on {lengths.device}")
-    return lengths
-
-
 def selective_scan_fwd(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False, reverse=False,
                        return_out=True, out_z_acc=None, out_z_max=None, initial_state=None, return_last_state=False,
                        checkpoints=True, lengths=None):
     """Returns (out, x, out_z|None) — the selective_scan_cuda.fwd contract.
-    lengths (inference on a zero-padded ragged batch, avse_scan_fwd_len): b row lengths, an int32 device tensor or a
-    sequence.  Row i is scanned over its first clamp(lengths[i], 0, l) columns only, exactly as the dense call scans
+    lengths (inference on a zero-padded ragged batch, avse_scan_fwd_len): b row lengths, an int32 device tensor, a
+    Lengths or a sequence.  Row i is scanned over its first clamp(lengths[i], 0, l) columns only, as the dense call scans
     the cropped row (reverse=True starts at the row's own last column); what the inputs hold past them is not used,
     the outputs are 0 there (out_z_acc keeps its values there) and out_z_max covers the valid columns.  No checkpoints
     are written (x is returned as None: no backward can follow); not together with the carried state below.
@@ -191,7 +179,7 @@ def selective_scan_fwd(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta
     if lengths is not None:
         if initial_state is not None or return_last_state is not False:
             raise RuntimeError("selective_scan_fwd: lengths cannot be combined with a carried state")
-        lengths = _row_lengths(lengths, b, u.device, "selective_scan_fwd")
+        lengths = as_lengths(lengths, b, l, u.device, "selective_scan_fwd", clamped=True).dev
         checkpoints = False
     stateful = lengths is None and (initial_state is not None or return_last_state is not False or not checkpoints)
     if stateful and (reverse or out_z_acc is not None or out_z_max is not None):
@@ -382,8 +370,8 @@ def _conv_state_arg(t, b, d, w, dt, dev):
 
 def causal_conv1d_fwd(x, weight, bias=None, silu=False, reverse=False, conv_state=None, lengths=None):
     """out = act(depthwise causal conv(x)) in x's dtype (fp32 or bf16; fp32 weights and arithmetic).
-    lengths (inference on a zero-padded ragged batch, avse_cconv_fwd_len): b row lengths, an int32 device tensor or a
-    sequence; row i is convolved over its first clamp(lengths[i], 0, l) columns exactly as the dense call convolves the
+    lengths (inference on a zero-padded ragged batch, avse_cconv_fwd_len): b row lengths, an int32 device tensor, a
+    Lengths or a sequence; row i is convolved over its first clamp(lengths[i], 0, l) columns as the dense call convolves the
     cropped row (reverse=True starts at the row's own last column), what x holds past them is not used and out is 0
     there.  Not together with conv_state.
     conv_state (streaming inference): a (b, d, w) tensor of x's dtype holding the row's last w inputs, oldest first
@@ -403,7 +391,7 @@ def causal_conv1d_fwd(x, weight, bias=None, silu=False, reverse=False, conv_stat
     if lengths is not None:
         if conv_state is not None:
             raise RuntimeError("causal_conv1d_fwd: lengths cannot be combined with a carried conv_state")
-        lengths = _row_lengths(lengths, b, x.device, "causal_conv1d_fwd")
+        lengths = as_lengths(lengths, b, l, x.device, "causal_conv1d_fwd", clamped=True).dev
         fn = _lib.lib().avse_cconv_fwd_len if dt == torch.float32 else _lib.lib().avse_cconv_fwd_len_bf16
         check(fn(b, d, l, w, ptr(x), x.stride(0), x.stride(1), ptr(lengths), ptr(weight), ptr(bias), ptr(out),
                  out.stride(0), out.stride(1), int(bool(silu)), int(bool(reverse)), stream_ptr(x.device)),
@@ -548,7 +536,7 @@ STFT_MIN_SAMPLES = 257          # reflect padding of n_fft / 2 = 256 samples nee
 
 def _wave_lengths(lengths, batch, extent, device, what):
     """Lengths of waveform rows for the STFT kernels: [257, extent] each (the reflect pad is undefined below)."""
-    lengths = _lengths(lengths, batch, extent, device, what)
+    lengths = as_lengths(lengths, batch, extent, device, what)
     if min(lengths.host) < STFT_MIN_SAMPLES:
         raise ValueError(f"{what}: a row of {min(lengths.host)} samples; reflect padding needs at least "
                          f"{STFT_MIN_SAMPLES}")
@@ -1311,7 +1299,7 @@ def bnact_fwd(x, gamma, beta, running_mean, running_var, training, momentum, eps
         Bn, T, inner, in_rows = _bn_time_geo(x, N, S, frames)
         if not 0 <= t_off < T:
             raise ValueError(f"bnact_fwd: t_off {t_off} outside the {T} time steps")
-        lengths = _lengths(lengths, Bn, T - t_off, x.device, "bnact_fwd")
+        lengths = as_lengths(lengths, Bn, T - t_off, x.device, "bnact_fwd")
         y = torch.empty_like(x)
         stats = torch.empty((C, 4), device=x.device, dtype=torch.float32)
         a = alpha.float().contiguous() if alpha is not None else None
@@ -1487,35 +1475,7 @@ def bnact_pool_frames_bwd(x, g, idx, stats, gamma, beta, act, alpha, training):
 
 # ------------------------------------------------------------------------ ragged batches (avse4 inference)
 
-class Lengths:
-    """Per-sample extents of a zero-padded ragged batch: the host values (validated without a device sync) and their
-    int32 device copy, made once and handed to every length-aware launch of a forward."""
-
-    def __init__(self, lengths, device):
-        host = lengths.tolist() if hasattr(lengths, "tolist") else list(lengths)
-        if not host or any(int(v) != v for v in host):
-            raise ValueError(f"lengths must be a non-empty sequence of integers, got {host}")
-        self.host = tuple(int(v) for v in host)
-        if min(self.host) < -2 ** 31 or max(self.host) >= 2 ** 31:
-            raise ValueError("lengths must fit int32")
-        self.dev = torch.tensor(self.host, dtype=torch.int32, device=device)
-
-    def checked(self, batch, extent, what):
-        """self after the host check 1 <= len <= extent for each of `batch` samples (ValueError otherwise)."""
-        if len(self.host) != batch:
-            raise ValueError(f"{what}: {len(self.host)} lengths for a batch of {batch}")
-        if min(self.host) < 1 or max(self.host) > extent:
-            raise ValueError(f"{what}: lengths must lie in [1, {extent}], got [{min(self.host)}, {max(self.host)}]")
-        return self
-
-
-def _lengths(lengths, batch, extent, device, what):
-    if not isinstance(lengths, Lengths):
-        lengths = Lengths(lengths, device)
-    elif lengths.dev.device != device:
-        raise ValueError(f"{what}: lengths live on {lengths.dev.device}, the tensors on {device}")
-    return lengths.checked(batch, extent, what)
-
+# every length-aware wrapper resolves its lengths argument with ragged.as_lengths
 
 def upsample_linear_len(v, vis_lengths, lengths, up, out):
     """out[b, :, :lengths[b]] = F.interpolate(v[b, :, :vis_lengths[b]], scale_factor=up, mode="linear") padded with 0 or
@@ -1525,8 +1485,8 @@ def upsample_linear_len(v, vis_lengths, lengths, up, out):
         raise ValueError(f"upsample_linear_len: v {tuple(v.shape)} and out {tuple(out.shape)} must be (B, C, *)")
     Bn, C, Tv = v.shape
     Kn = out.shape[2]
-    vl = _lengths(vis_lengths, Bn, Tv, v.device, "upsample_linear_len (vis_lengths)")
-    kl = _lengths(lengths, Bn, Kn, v.device, "upsample_linear_len (lengths)")
+    vl = as_lengths(vis_lengths, Bn, Tv, v.device, "upsample_linear_len (vis_lengths)")
+    kl = as_lengths(lengths, Bn, Kn, v.device, "upsample_linear_len (lengths)")
     _need_gpu(v, out)
     if v.dtype != torch.float32 or out.dtype != torch.float32 or v.stride(2) != 1 or out.stride(2) != 1:
         raise ValueError("upsample_linear_len: fp32 tensors with unit stride along time")
@@ -1545,8 +1505,8 @@ def gather_nearest_len(v, vis_lengths, lengths, T, extra=0, out=None):
     if v.dim() != 3:
         raise ValueError(f"gather_nearest_len: v {tuple(v.shape)} must be (B, Tv, C)")
     Bn, Tv, C = v.shape
-    vl = _lengths(vis_lengths, Bn, Tv, v.device, "gather_nearest_len (vis_lengths)")
-    tl = _lengths(lengths, Bn, T, v.device, "gather_nearest_len (lengths)")
+    vl = as_lengths(vis_lengths, Bn, Tv, v.device, "gather_nearest_len (vis_lengths)")
+    tl = as_lengths(lengths, Bn, T, v.device, "gather_nearest_len (lengths)")
     _need_gpu(v)
     if out is None:
         out = torch.empty((Bn, T, C + extra), device=v.device, dtype=torch.float32)
@@ -1574,16 +1534,7 @@ def gln_cl_fwd(x, gamma, beta, eps, lengths, len_axis, res=None, transpose_out=F
     if len_axis not in (0, 1):
         raise ValueError(f"gln_cl_fwd: len_axis must be 0 or 1, got {len_axis}")
     Bn, R, C, N = x.shape
-    if torch.is_tensor(lengths) and lengths.is_cuda:
-        if lengths.dtype != torch.int32 or tuple(lengths.shape) != (Bn,) or lengths.device != x.device:
-            raise ValueError(f"gln_cl_fwd: lengths must be {Bn} int32 entries on {x.device}")
-        ldev = lengths.contiguous()
-    else:
-        ln = lengths if isinstance(lengths, Lengths) else Lengths(lengths, x.device)
-        extent = (R, C)[len_axis]
-        if len(ln.host) != Bn or min(ln.host) < 0 or max(ln.host) > extent or ln.dev.device != x.device:
-            raise ValueError(f"gln_cl_fwd: {Bn} lengths in [0, {extent}] on {x.device}, got {ln.host}")
-        ldev = ln.dev
+    ldev = as_lengths(lengths, Bn, (R, C)[len_axis], x.device, "gln_cl_fwd", clamped=True).dev
     _need_gpu(x, gamma, beta, res)
     x = x.contiguous()
     y = torch.empty((Bn, C, R, N) if transpose_out else (Bn, R, C, N), device=x.device, dtype=torch.float32)
@@ -1606,7 +1557,7 @@ def prelu_gln_fwd(x, alpha, gamma, beta, eps=1e-8, lengths=None):
     """gLN(PReLU(x)) on (B, C, K); returns (y, stats (B, 2) = mean, rstd).  lengths (a sequence or a Lengths, inference
     only): sample b is normalised over its first lengths[b] columns alone and y is 0 past them (avse_prelu_gln_fwd_len)."""
     if lengths is not None:
-        lengths = _lengths(lengths, x.shape[0], x.shape[2], x.device, "prelu_gln_fwd")
+        lengths = as_lengths(lengths, x.shape[0], x.shape[2], x.device, "prelu_gln_fwd")
     _need_gpu(x, alpha, gamma, beta)
     x = x.float().contiguous()
     Bn, C, Kn = x.shape
@@ -1661,7 +1612,7 @@ def dwconv_fwd(x, w, dilation, lengths=None):
     """Depthwise 'same' conv1d.  lengths (inference only): x reads as 0 past lengths[b] whatever it holds there and y
     is 0 there (avse_dwconv_fwd_len)."""
     if lengths is not None:
-        lengths = _lengths(lengths, x.shape[0], x.shape[2], x.device, "dwconv_fwd")
+        lengths = as_lengths(lengths, x.shape[0], x.shape[2], x.device, "dwconv_fwd")
     _need_gpu(x, w)
     x = x.float().contiguous()
     Bn, C, Kn = x.shape
@@ -1725,7 +1676,7 @@ def dwconv_gln_fwd(x, w, dilation, alpha, gamma, beta, eps=1e-8, planes=False, l
     (PLANES_ATTR).  lengths (inference only): sample b is its first lengths[b] columns alone, y (or the planes) is 0
     past them and y1 is not written there (avse_dwconv_gln_fwd_len / _q_len)."""
     if lengths is not None:
-        lengths = _lengths(lengths, x.shape[0], x.shape[2], x.device, "dwconv_gln_fwd")
+        lengths = as_lengths(lengths, x.shape[0], x.shape[2], x.device, "dwconv_gln_fwd")
     _need_gpu(x, w, alpha, gamma, beta)
     x = x.float().contiguous()
     Bn, C, Kn = x.shape

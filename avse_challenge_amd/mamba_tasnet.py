@@ -22,6 +22,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import kernels as K
+from .ragged import as_lengths, pad_stack, run_planned
 
 NSTATE = 16
 # bf16 autocast (BASELINE configs[4]): the projections then run as bf16 GEMMs and the conv / scan on bf16
@@ -782,9 +783,9 @@ class MaskNet(nn.Module):
 
     @torch.no_grad()
     def forward_ragged(self, mixture_w, frame_lengths):     # forward() with the Mamba blocks' length-aware path
-        x = mixture_w.permute(0, 2, 1)
+        x = mixture_w.permute(0, 2, 1)                      # frame_lengths: the forward's ragged.Lengths
         Bn, L, D = x.shape
-        h = self.mamba_net.forward_ragged(self.bottleneck_conv1x1(self.layer_norm(x)), frame_lengths)
+        h = self.mamba_net.forward_ragged(self.bottleneck_conv1x1(self.layer_norm(x)), frame_lengths.dev)
         y = self.mask_conv1x1(h)
         return F.relu(y.reshape(Bn, L, self.n_spk, D).permute(2, 0, 3, 1))
 
@@ -814,7 +815,62 @@ class Decoder(nn.ConvTranspose1d):
         return F.fold(frames, (1, T), (1, k), stride=(1, s))[:, 0, 0, :]
 
 
-class MambaTasNet(nn.Module):
+class RaggedSeparation:
+    """forward_ragged and separate_batch of an encoder / masknet / decoder model (MambaTasNet, dpmamba.DPMambaTasNet)."""
+
+    zero_encoder_padding = False    # select the encoder output to 0 past each row's frames before the mask network too
+
+    @torch.no_grad()
+    def forward_ragged(self, mix, lengths):
+        """forward() for a batch of mixtures of different lengths in one pass (inference, fp32): mix (B, T_max) holds
+        utterance b in its first lengths[b] samples -> (B, T_max, n_spk) whose row b holds forward(mix[b:b+1,
+        :lengths[b]]) in its first lengths[b] samples and 0 after them.  What mix holds past an utterance is not used.
+
+        Utterance b has L_b = (T_b - k) // hop + 1 encoder frames.  The mask network runs its length-aware path on the
+        frame Lengths made here, once (Mamba-TasNet: all else in it acts per frame; zero_encoder_padding: its norms read
+        the padding frames, which would hold samples of the utterance's last hop), and the masked encoder output is
+        selected to 0 from frame L_b on before the decoder's overlap-add, which would fold frame L_b into the last hop
+        samples.  Samples from (L_b - 1) hop + k on are 0, the F.pad of train_wsj0mix.py:86-111: the utterance alone
+        gives the same zeros when (T_b - k) % hop != 0."""
+        K._need_gpu(mix)
+        if _autocast_dtype() is not None:
+            raise RuntimeError(f"{type(self).__name__}.forward_ragged runs in fp32 (the bf16 autocast path is not built)")
+        k, hop = self.encoder.conv1d.kernel_size[0], self.encoder.conv1d.stride[0]
+        B, T = mix.shape
+        tl = as_lengths(lengths, B, T, mix.device, "forward_ragged")
+        if min(tl.host) < k:
+            raise ValueError(f"forward_ragged: every utterance needs at least one encoder window of {k} samples, got "
+                             f"{min(tl.host)}")
+        fl = tl.map(lambda t: (t - k) // hop + 1)                         # once per forward, for every layer
+        zero = mix.new_zeros(())
+        mix = torch.where(tl.valid(T), mix, zero)                         # a select: NaN in the padding is dropped
+        mix_w = self.encoder(mix)                                         # (B, N, L_max)
+        f_ok = fl.valid(mix_w.shape[-1])                                  # (B, L_max)
+        if self.zero_encoder_padding:
+            mix_w = torch.where(f_ok[:, None, :], mix_w, zero)
+        est_mask = self.masknet.forward_ragged(mix_w, fl)
+        sep_h = torch.where(f_ok[None, :, None, :], mix_w.unsqueeze(0) * est_mask, zero)
+        est = torch.stack([self.decoder(sep_h[i]) for i in range(self.num_spks)], dim=-1)
+        est = F.pad(est, (0, 0, 0, T - est.shape[1])) if T > est.shape[1] else est[:, :T, :]
+        t_ok = torch.arange(T, device=mix.device)[None, :] < ((fl.dev - 1) * hop + k)[:, None]
+        return torch.where(t_ok[:, :, None], est, zero)
+
+    def separate_batch(self, mixes, batch_size=8, max_pad_ratio=1.25):
+        """Separate a list of 1-D mixtures (tensors or arrays) of different lengths in length-planned padded batches
+        (ragged.plan_ragged_batches on the sample counts, one forward_ragged per batch): -> the list of (T_b, n_spk)
+        float32 arrays in input order, each what forward() returns for the utterance alone (to fp32 rounding)."""
+        import numpy as np
+        dev = next(self.parameters()).device
+        waves = [np.asarray(m.detach().cpu() if torch.is_tensor(m) else m, dtype=np.float32).reshape(-1) for m in mixes]
+
+        def run(idx):
+            pad, tl = pad_stack(waves, 0, idx)
+            est = self.forward_ragged(torch.from_numpy(pad).to(dev), tl).cpu().numpy()
+            return [est[r, :t].copy() for r, t in enumerate(tl)]
+        return run_planned([w.shape[0] for w in waves], batch_size, max_pad_ratio, run)
+
+
+class MambaTasNet(RaggedSeparation, nn.Module):
     """Encoder / MaskNet / Decoder with compute_forward semantics (train_wsj0mix.py:86-111)."""
 
     def __init__(self, N=512, kernel_size=16, n_mamba=32, n_spk=2, d_state=16, expand=2, d_conv=4,
@@ -835,64 +891,6 @@ class MambaTasNet(nn.Module):
         if T > est.shape[1]:
             return F.pad(est, (0, 0, 0, T - est.shape[1]))
         return est[:, :T, :]
-
-    @torch.no_grad()
-    def forward_ragged(self, mix, lengths):
-        """forward() for a batch of mixtures of different lengths in one pass (inference, fp32): mix (B, T_max) holds
-        utterance b in its first lengths[b] samples -> (B, T_max, n_spk) whose row b holds forward(mix[b:b+1,
-        :lengths[b]]) in its first lengths[b] samples and 0 after them.  What mix holds past an utterance is not used.
-
-        Utterance b has L_b = (T_b - k) // hop + 1 encoder frames.  Everything in the model acts per frame except the
-        BiMamba blocks (whose time-reversed direction would start in the padding: BiMambaV2.forward_ragged) and the
-        decoder's overlap-add (the padded frame L_b would reach into the last hop samples of the utterance: the masked
-        encoder output is set to 0 from frame L_b on).  Samples from (L_b - 1) hop + k on are 0, the F.pad of
-        train_wsj0mix.py:86-111: the utterance alone gives the same zeros when (T_b - k) % hop != 0."""
-        K._need_gpu(mix)
-        if _autocast_dtype() is not None:
-            raise RuntimeError("MambaTasNet.forward_ragged runs in fp32 (the bf16 autocast path is not built)")
-        k, hop = self.encoder.conv1d.kernel_size[0], self.encoder.conv1d.stride[0]
-        host = [int(v) for v in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
-        B, T = mix.shape
-        if len(host) != B or max(host) > T:
-            raise ValueError(f"forward_ragged: {B} lengths of at most {T} samples, got {host}")
-        if min(host) < k:
-            raise ValueError(f"forward_ragged: every utterance needs at least one encoder window of {k} samples, got "
-                             f"{min(host)}")
-        dev = mix.device
-        frames = [(t - k) // hop + 1 for t in host]
-        t_len = torch.tensor(host, device=dev)
-        f_len = torch.tensor(frames, dtype=torch.int32, device=dev)       # once per forward, for every layer
-        zero = mix.new_zeros(())
-        t_idx = torch.arange(T, device=dev)
-        mix = torch.where(t_idx[None, :] < t_len[:, None], mix, zero)     # a select: NaN in the padding is dropped
-        mix_w = self.encoder(mix)                                         # (B, N, L_max)
-        est_mask = self.masknet.forward_ragged(mix_w, f_len)
-        f_ok = torch.arange(mix_w.shape[-1], device=dev)[None, :] < f_len[:, None]            # (B, L_max)
-        sep_h = torch.where(f_ok[None, :, None, :], mix_w.unsqueeze(0) * est_mask, zero)
-        est = torch.stack([self.decoder(sep_h[i]) for i in range(self.num_spks)], dim=-1)
-        est = F.pad(est, (0, 0, 0, T - est.shape[1])) if T > est.shape[1] else est[:, :T, :]
-        t_ok = t_idx[None, :] < ((f_len.long() - 1) * hop + k)[:, None]
-        return torch.where(t_ok[:, :, None], est, zero)
-
-    def separate_batch(self, mixes, batch_size=8, max_pad_ratio=1.25):
-        """Separate a list of 1-D mixtures (tensors or arrays) of different lengths in length-planned padded batches
-        (avse4.plan_ragged_batches on the sample counts, one forward_ragged per batch): -> the list of (T_b, n_spk)
-        float32 arrays in input order, each what forward() returns for the utterance alone (to fp32 rounding)."""
-        import numpy as np
-
-        from .avse4 import plan_ragged_batches
-        dev = next(self.parameters()).device
-        waves = [np.asarray(m.detach().cpu() if torch.is_tensor(m) else m, dtype=np.float32).reshape(-1) for m in mixes]
-        out = [None] * len(waves)
-        for idx in plan_ragged_batches([w.shape[0] for w in waves], batch_size, max_pad_ratio):
-            tl = [waves[i].shape[0] for i in idx]
-            pad = np.zeros((len(idx), max(tl)), np.float32)
-            for r, i in enumerate(idx):
-                pad[r, :tl[r]] = waves[i]
-            est = self.forward_ragged(torch.from_numpy(pad).to(dev), tl).cpu().numpy()
-            for r, i in enumerate(idx):
-                out[i] = est[r, :tl[r]].copy()
-        return out
 
 
 class StreamingSeparator:

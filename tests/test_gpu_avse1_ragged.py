@@ -16,24 +16,16 @@ import pytest
 import torch
 
 import _dirty
+import _ragged
+from _ragged import errors
 from oracle import avse1_ref, stft_ref
 from oracle.det_init import det_init_, det_input
-from oracle.losses_ref import si_sdr_db
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 T_LEN, TV_LEN, HW = (16000, 9215, 6000), (25, 14, 9), 96
 F_LEN = tuple(1 + t // 128 for t in T_LEN)
 PAD_RATIO = 2.0           # 3 x 16000 padded / 31215 useful samples = 1.54: the planner keeps the three in one batch
-
-
-def errors(est, ref, clean):
-    """(RMS error, its bar, |dSI-SDR| in dB) of test_gpu_fullsize.check_waveforms."""
-    est, ref, clean = (torch.as_tensor(np.asarray(a)).double() for a in (est, ref, clean))
-    rms = float((est - ref).pow(2).mean().sqrt())
-    bar = 1e-4 * max(1.0, float(ref.pow(2).mean().sqrt()))
-    d = float((si_sdr_db(clean, est) - si_sdr_db(clean, ref)).abs().max())
-    return rms, bar, d
 
 
 def oracle_enhance(ref, noisy, lips):
@@ -74,9 +66,7 @@ def run_padded(m, audio, lips):
 @pytest.fixture(scope="module")
 def case():
     from avse_challenge_amd import avse1
-    torch.backends.cuda.matmul.allow_tf32 = False
-    torch.backends.cudnn.allow_tf32 = False
-    torch.set_num_threads(16)
+    _ragged.fp32_math()
     items = [{"noisy_audio": 0.1 * det_input((t,), 7100 + b), "clean": 0.1 * det_input((t,), 7120 + b),
               "lip_images": det_input((3, tv, HW, HW), 7110 + b, "uint8")}
              for b, (t, tv) in enumerate(zip(T_LEN, TV_LEN))]

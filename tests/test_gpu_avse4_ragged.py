@@ -14,24 +14,16 @@ import pytest
 import torch
 
 import _dirty
+import _ragged
+from _ragged import errors
 from oracle import avse4_ref
 from oracle.det_init import det_init_, det_input
-from oracle.losses_ref import si_sdr_db
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 KW = dict(N=64, L=40, B=64, H=128, P=3, X=3, R=2, C=2)
 T_LEN, TV_LEN = (16000, 9215, 12000), (25, 14, 20)
 K_LEN = tuple((t - 40) // 20 + 1 for t in T_LEN)
-
-
-def errors(est, ref, clean):
-    """(RMS error, its bar, max |dSI-SDR| in dB) of test_gpu_fullsize.check_waveforms."""
-    est, ref, clean = (torch.as_tensor(np.asarray(a)).double() for a in (est, ref, clean))
-    rms = float((est - ref).pow(2).mean().sqrt())
-    bar = 1e-4 * max(1.0, float(ref.pow(2).mean().sqrt()))
-    d = float((si_sdr_db(clean, est) - si_sdr_db(clean, ref)).abs().max())
-    return rms, bar, d
 
 
 def passes(est, ref, clean):
@@ -51,9 +43,7 @@ def padded_inputs(items, fill):
 @pytest.fixture(scope="module")
 def case():
     from avse_challenge_amd import avse4
-    torch.backends.cuda.matmul.allow_tf32 = False
-    torch.backends.cudnn.allow_tf32 = False
-    torch.set_num_threads(16)
+    _ragged.fp32_math()
     items = [{"noisy_audio": 0.1 * det_input((2, t), 5100 + b),
               "vis_feat": det_input((1, tv, 112, 112), 5110 + b, "uniform"),
               "clean": 0.1 * det_input((2, t), 5120 + b)} for b, (t, tv) in enumerate(zip(T_LEN, TV_LEN))]
@@ -133,14 +123,10 @@ def test_f_the_tool_enhances_a_directory(case, tmp_path):
     for the default-size model) on the three utterances: scenes found -> planned batches -> <scene>.wav; each file is
     the enhance_batch estimate of what the tool read (the PCM_16 noisy wav) to the PCM_16 step, an existing file is
     left alone, and a second run finds nothing to do."""
-    import importlib.util
     import os
 
     from avse_challenge_amd import ckpt_io
-    here = os.path.dirname(os.path.abspath(__file__))
-    spec = importlib.util.spec_from_file_location("avse4_enhance", os.path.join(here, "..", "tools", "avse4_enhance.py"))
-    tool = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(tool)
+    tool = _ragged.load_tool("avse4_enhance")
     noisy, lips, out = (str(tmp_path / d) for d in ("noisy", "lips", "out"))
     for d in (noisy, lips, out):
         os.mkdir(d)

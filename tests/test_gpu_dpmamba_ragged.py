@@ -10,17 +10,17 @@ tests/test_gpu_fullsize.py: waveform RMS <= 1e-4 max(1, RMS(ref)) and |dSI-SDR| 
 0.1 det_input((t, 2), 6220 + b) as the clean signals.  On the CPU the oracle run on the zero-padded batch misses that
 bar by 148x to 369x for the three shorter utterances: every GroupNorm(1, N) of the dual-path model takes its statistics
 over the whole padded sample.  The oracle runs once per model (module fixture); all GPU work allocates dirty."""
-import importlib.util
-import os
+import functools
 
 import numpy as np
 import pytest
 import torch
 
 import _dirty
+import _ragged
+from _ragged import padded
 from oracle import dpmamba_ref
 from oracle.det_init import det_init_, det_input
-from oracle.losses_ref import si_sdr_db
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -29,28 +29,13 @@ T_LEN = (4000, 2307, 3000, 3008)
 K_LEN = tuple((t - 16) // 8 + 1 for t in T_LEN)
 
 
-def errors(est, ref, clean):
-    """(RMS error, its bar, max |dSI-SDR| in dB) of test_gpu_fullsize.check_waveforms; all (T, n_spk)."""
-    est, ref, clean = (torch.as_tensor(np.asarray(a)).double().T for a in (est, ref, clean))
-    rms = float((est - ref).pow(2).mean().sqrt())
-    bar = 1e-4 * max(1.0, float(ref.pow(2).mean().sqrt()))
-    d = float((si_sdr_db(clean, est) - si_sdr_db(clean, ref)).abs().max())
-    return rms, bar, d
-
-
-def padded(mixes, fill):
-    mix = torch.full((len(mixes), max(m.shape[0] for m in mixes)), fill)
-    for b, m in enumerate(mixes):
-        mix[b, :m.shape[0]] = m
-    return mix.to(DEV)
+errors = functools.partial(_ragged.errors, time_first=True)               # all (T, n_spk)
 
 
 @pytest.fixture(scope="module", params=[True, False], ids=["skip", "noskip"])
 def case(request):
     from avse_challenge_amd import dpmamba as M
-    torch.backends.cuda.matmul.allow_tf32 = False
-    torch.backends.cudnn.allow_tf32 = False
-    torch.set_num_threads(16)
+    _ragged.fp32_math()
     mixes = [0.1 * det_input((t,), 6200 + b) for b, t in enumerate(T_LEN)]
     clean = [0.1 * det_input((t, 2), 6220 + b) for b, t in enumerate(T_LEN)]
     short = 0.1 * det_input((16,), 6204)                                  # one encoder frame, two chunks
@@ -152,31 +137,4 @@ def test_g_the_tool_separates_a_directory(case, tmp_path):
     """tools/mamba_separate.py (separate_dir) with a DPMamba model on three mixtures: the files test_g of
     tests/test_gpu_mamba_ragged.py expects, each the peak-normalised separate_batch estimate of what the tool read to
     the PCM_16 step; an existing output is left alone and a second run finds nothing to do."""
-    from avse_challenge_amd import ckpt_io
-    here = os.path.dirname(os.path.abspath(__file__))
-    spec = importlib.util.spec_from_file_location("mamba_separate", os.path.join(here, "..", "tools", "mamba_separate.py"))
-    tool = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(tool)
-    mix, out, s1, s2 = (str(tmp_path / d) for d in ("mix", "out", "s1", "s2"))
-    for d in (mix, out, s1, s2):
-        os.mkdir(d)
-    for b, x in enumerate(case["mixes"][:3]):
-        ckpt_io.write_wav(os.path.join(mix, f"u{b}.wav"), x.numpy(), 8000)
-        for k, d in enumerate((s1, s2)):
-            ckpt_io.write_wav(os.path.join(d, f"u{b}.wav"), case["clean"][b][:, k].numpy(), 8000)
-    for k in (1, 2):                                                      # there already: not redone
-        ckpt_io.write_wav(os.path.join(out, f"itemu2_source{k}hat.wav"), np.zeros(10), 8000)
-    assert tool.separate_dir(case["m"], mix, out, batch_size=2, target_dirs=[s1, s2]) == ["u0", "u1"]
-    assert sorted(os.listdir(out)) == sorted([f"itemu{b}_source{k}hat.wav" for b in range(3) for k in (1, 2)] +
-                                             ["test_results.csv"])
-    assert ckpt_io.read_wav(os.path.join(out, "itemu2_source1hat.wav"))[0].shape == (10,)
-    read = [tool.load_wav(os.path.join(mix, f"u{b}.wav"), 8000)[0] for b in (0, 1)]
-    for b, est in enumerate(case["m"].separate_batch(read, batch_size=2)):
-        for k in (0, 1):
-            wav, sr = ckpt_io.read_wav(os.path.join(out, f"itemu{b}_source{k + 1}hat.wav"))
-            assert sr == 8000 and wav.shape == (T_LEN[b],)
-            assert float(np.abs(wav - est[:, k] / np.max(np.abs(est[:, k]))).max()) <= 1.5 / 32768
-    rows = open(os.path.join(out, "test_results.csv")).read().strip().splitlines()
-    assert rows[0] == "snt_id,si-snr,si-snr_i" and [r.split(",")[0] for r in rows[1:]] == ["u0", "u1", "avg"]
-    assert all(np.isfinite(float(v)) for r in rows[1:] for v in r.split(",")[1:])
-    assert tool.find_mixtures(mix, out, 2) == [] and tool.separate_dir(case["m"], mix, out, batch_size=2) == []
+    _ragged.check_separate_dir(case["m"], case["mixes"][:3], case["clean"], tmp_path)

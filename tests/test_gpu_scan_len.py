@@ -233,3 +233,27 @@ def test_f_conv_on_the_padded_time_stride(dtype, monkeypatch):
                 with _dirty.dirty(monkeypatch):
                     dense = K().causal_conv1d_fwd(x[b:b + 1, :, :n], w, bias, silu=True, reverse=reverse)
                 assert torch.equal(out[b, :, :n], dense[0]), (b, n, reverse)
+
+
+# ------------------------------------------------------------------ one resolver for the three ways to give lengths
+
+def test_g_a_list_a_lengths_and_a_device_tensor_give_the_same_bits(monkeypatch):
+    """selective_scan_fwd, causal_conv1d_fwd and gln_cl_fwd (the smallest shape of tests/test_gpu_gln_cl_len.py) with the
+    same lengths as a list, a Lengths and an int32 device tensor; each set holds a full and an empty row."""
+    ins = scan_inputs(torch.float32)
+    x, w, bias = conv_inputs(*CONV_CASES[0], torch.float32)
+    gl = (7, 6, 1, 0, 3)
+    gx = (1.5 * det_input((5, 7, 10, 5), 4305) + 0.3).to(DEV)
+    gg, gb = (1.0 + 0.3 * det_input((5,), 4310)).to(DEV), (0.1 * det_input((5,), 4311)).to(DEV)
+
+    def three_ways(lens):
+        return [list(lens), K().Lengths(lens, torch.device(DEV, 0)), torch.tensor(lens, dtype=torch.int32, device=DEV)]
+    with _dirty.dirty(monkeypatch):
+        scans = [K().selective_scan_fwd(**ins, delta_softplus=True, lengths=ln) for ln in three_ways(LENS)]
+        convs = [K().causal_conv1d_fwd(x, w, bias, silu=True, lengths=ln) for ln in three_ways(CONV_CASES[0][1])]
+        glns = [K().gln_cl_fwd(gx, gg, gb, 1e-8, ln, 0) for ln in three_ways(gl)]
+    for other in (1, 2):
+        assert torch.equal(scans[0][0], scans[other][0]) and torch.equal(scans[0][2], scans[other][2]), other
+        assert torch.equal(convs[0], convs[other]), other
+        assert torch.equal(glns[0][0], glns[other][0]) and torch.equal(glns[0][1], glns[other][1]), other
+    assert bool(scans[0][2][0].any()) and bool(convs[0][0].any()) and bool(glns[0][0][0].any())     # the full rows ran

@@ -11,7 +11,7 @@ For every `<scene><noisy-suffix>.wav` in --noisy with a `<scene>.npy` in --lips 
 dataset hands them to the model, (3, Tv, H, W) uint8 or float (dataset.py:120-152; decoding the mp4 is left to the
 caller; not needed with --a-only) -- it writes `<save-root>/<model-uid>/<scene>.wav` (PCM_16, 16 kHz,
 ckpt_io.write_wav) unless that file exists already, as test.py does.  Scenes are sorted by length and cut into batches
-by avse4.plan_ragged_batches inside AVNet.enhance_batch.
+by ragged.plan_ragged_batches inside AVNet.enhance_batch.
 
 --bench times, on a seeded synthetic set (noise at 16 kHz, lengths uniform in [min-s, max-s], 25 fps uint8 lips of
 96 x 96) and the default-size model with det_init_ weights in eval mode with the channels-last trunks, the loop of
@@ -20,7 +20,6 @@ passes between two device events with the arms alternating; host-side padding, t
 the timed span for both arms.  Prints one JSON line.  A run without a GPU fails; nothing here falls back.
 """
 import argparse
-import json
 import os
 import sys
 
@@ -31,8 +30,9 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-from avse_challenge_amd import avse1, avse4, ckpt_io  # noqa: E402
+sys.path[:0] = [REPO, os.path.join(REPO, "tools")]
+import ragged_bench  # noqa: E402
+from avse_challenge_amd import avse1, ckpt_io  # noqa: E402
 
 SAMPLE_RATE = 16000
 
@@ -84,15 +84,6 @@ def synthetic_set(n, min_s, max_s, hw=96, seed=0):
     return items
 
 
-def _timed_ms(fn):
-    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    start.record()
-    fn()
-    end.record()
-    end.synchronize()
-    return start.elapsed_time(end)
-
-
 def bench(a):
     from oracle.det_init import det_init_
     torch.backends.cuda.matmul.allow_tf32 = False
@@ -102,40 +93,16 @@ def bench(a):
     model = det_init_(avse1.AVNet(), 0).to("cuda").eval()
     model.net_audiofeat.use_channels_last()
     model.net_visualfeat.use_channels_last()
-    sizes = [int(v) for v in a.batch_sizes.split(",")]
-    plans = {bs: avse4.plan_ragged_batches(lengths, bs, a.max_pad_ratio) for bs in sizes}
 
     def loop():
         for d in items:
             model.enhance(torch.from_numpy(d["noisy_audio"])[None].to("cuda"),
                           torch.from_numpy(d["lip_images"])[None].to("cuda"))[0].cpu().numpy()
 
-    arms = {"enhance_loop": loop,
-            **{f"enhance_batch_{bs}": (lambda bs=bs: model.enhance_batch(items, bs, a.max_pad_ratio)) for bs in sizes}}
-    for fn in arms.values():                                 # the untimed pass
-        fn()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in arms}
-    for _ in range(a.repeats):
-        for k, fn in arms.items():
-            ms[k].append(_timed_ms(fn))
-    rec = {"metric": "avse1_enhance_utterances_per_s", "unit": "utterances/s", "model": "avse1 AVNet",
-           "utterances": a.utterances, "seconds_of_audio": round(sum(lengths) / SAMPLE_RATE, 1), "min_s": a.min_s,
-           "max_s": a.max_s, "max_pad_ratio": a.max_pad_ratio, "repeats": a.repeats,
-           "max_stft_frames": 1 + max(lengths) // 128, "device": torch.cuda.get_device_name(0), "arms": {}}
-    for k, v in ms.items():
-        rec["arms"][k] = {"utterances_per_s": round(a.utterances / (min(v) * 1e-3), 2),
-                          "ms_per_pass": [round(x, 1) for x in v]}
-    for bs, p in plans.items():
-        pad = sum(max(lengths[i] for i in b) * len(b) for b in p) / sum(lengths)
-        rec["arms"][f"enhance_batch_{bs}"].update(batches=len(p), padded_over_useful=round(pad, 3))
-    rec["max_mem_gb"] = round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)
-    line = json.dumps(rec)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    ragged_bench.run(a, {"metric": "avse1_enhance_utterances_per_s", "unit": "utterances/s", "model": "avse1 AVNet"},
+                     lengths, SAMPLE_RATE, "enhance_loop", loop, "enhance_batch",
+                     lambda bs, plan: model.enhance_batch(items, bs, a.max_pad_ratio),
+                     extra={"max_stft_frames": 1 + max(lengths) // 128})
 
 
 def main(argv=None):
@@ -150,12 +117,7 @@ def main(argv=None):
     ap.add_argument("--batch-size", type=int, default=16)
     ap.add_argument("--max-pad-ratio", type=float, default=1.25)
     ap.add_argument("--bench", action="store_true", help="time enhance_batch against the enhance() loop")
-    ap.add_argument("--utterances", type=int, default=64)
-    ap.add_argument("--min-s", type=float, default=3.0)
-    ap.add_argument("--max-s", type=float, default=9.0)
-    ap.add_argument("--batch-sizes", default="4,16,32")
-    ap.add_argument("--repeats", type=int, default=3)
-    ap.add_argument("--out", default=None, help="--bench: also write the line to this file")
+    ragged_bench.add_args(ap, repeats=3, out_help="--bench: also write the line to this file")
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("avse1_enhance needs the GPU")

@@ -8,7 +8,7 @@ For every `<scene><noisy-suffix>.wav` in --noisy with a `<scene>.npy` in --lips 
 (Tv, 112, 112) float32 as the reference's dataset.process_frames (dataset.py:157-170) makes them from the scene's
 mp4; decoding the mp4 is left to the caller -- it writes `<out>/<scene>.wav` (PCM_16, 16 kHz, ckpt_io.write_wav) unless
 that file exists already, as test.py does.  Scenes are sorted by length and cut into batches by
-avse4.plan_ragged_batches; each batch is one AVSE4BaselineModule.enhance_batch call.  The output directory is what
+ragged.plan_ragged_batches; each batch is one AVSE4BaselineModule.enhance_batch call.  The output directory is what
 tools/mbstoi_eval.py reads (with --enhanced-suffix "").
 """
 import argparse
@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from avse_challenge_amd import avse4, ckpt_io  # noqa: E402
+from avse_challenge_amd import avse4, ckpt_io, ragged  # noqa: E402
 
 SAMPLE_RATE = 16000
 
@@ -48,16 +48,16 @@ def load_item(noisy, lips, name, noisy_suffix="_mix", num_channels=2):
 
 
 def enhance_dir(model, noisy, lips, out, noisy_suffix="_mix", batch_size=16, max_pad_ratio=1.25):
-    """Writes <out>/<scene>.wav for every scene found; returns the scene names written, in writing order."""
+    """Writes <out>/<scene>.wav for every scene found; returns the scene names written."""
     os.makedirs(out, exist_ok=True)
     names = find_scenes(noisy, lips, out, noisy_suffix)
     items = [load_item(noisy, lips, n, noisy_suffix, model.num_channels) for n in names]
-    written = []
-    for batch in avse4.plan_ragged_batches([d["noisy_audio"].shape[-1] for d in items], batch_size, max_pad_ratio):
+
+    def run(batch):
         for i, (_, _, est) in zip(batch, model.enhance_batch([items[i] for i in batch])):
             ckpt_io.write_wav(os.path.join(out, names[i] + ".wav"), est.T, SAMPLE_RATE)      # test.py:46
-            written.append(names[i])
-    return written
+        return [names[i] for i in batch]
+    return ragged.run_planned([d["noisy_audio"].shape[-1] for d in items], batch_size, max_pad_ratio, run)
 
 
 def main(argv=None):

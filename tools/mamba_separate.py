@@ -8,7 +8,7 @@ utterance per step.
 
 For every `<id>.wav` in --mix it writes `<out>/item<id>_source<k>hat.wav` (k = 1 .. n_spk; PCM_16, each source divided
 by its peak as save_audio does) unless all of an utterance's files exist already.  Utterances are sorted by length
-and cut into batches by avse4.plan_ragged_batches; each batch is one forward_ragged call of the model the hparams
+and cut into batches by ragged.plan_ragged_batches; each batch is one forward_ragged call of the model the hparams
 describe (MambaTasNet.separate_batch, DPMambaTasNet.separate_batch).  With --targets (one directory per speaker,
 holding `<id>.wav` too) it also writes `<out>/test_results.csv` with the columns snt_id, si-snr, si-snr_i and a final
 avg row, from losses.si_snr_pit on the unnormalised estimates, for the utterances separated in this run.  The
